@@ -16,23 +16,36 @@ A "step" = one compute() + train() over synthetic rollout buffers (SURVEY.md 8d 
 region.  One transition = one (t, n) environment step for all agents.
 Multi-GPU (`--gpus N`, N > 1; `--scaling auto`, the default): the ONE line answers the BASELINE's question -- `value` is the
 STRONG-scaling figure at the n_rollout_threads the BASELINE quotes the workload on (4096 global for mpe, 8192 for cheetah6 =
-configs[2], split over the ranks; `scaling: "strong"`, `config.n_rollout_threads_global`), and the `weak` object carries the
-weak-scaling figure of the same job (every rank at the config's single-GPU size), timed in a region of its own right after.
+configs[2], split over the ranks; `scaling: "strong"`, `config.n_rollout_threads_global`), and with `--full` the `weak` object
+carries the weak-scaling figure of the same job (every rank at the config's single-GPU size), timed in a region of its own right after.
 `config.ranks_seen` = a SUM all-reduce of ones over the update's communicator (not WORLD_SIZE from the environment).
 `--scaling weak|strong` time only that one figure (`--global-threads`, `--threads-per-gpu` override the sizes).
 Gradients / loss scalars are all-reduced each optimiser step (one message per step, harl_amd/dist.py: RCCL, or the one-hop
 hipIpc exchange with HARL_ALLREDUCE=auto|oneshot);
 `--dist-single` initialises the nccl(=RCCL) process group even with one rank so that branch runs on a 1-GPU box.
 
-    python bench.py --gpus 1 --steps 5 --warmup 2 [--config cheetah6]
+    python bench.py --gpus 1 --steps 5 --warmup 2 [--config cheetah6] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port P \\
         bench.py --gpus 8 --steps 5 --warmup 2
 
-The default run (mpe) appends the three other BASELINE workloads and the coverage workload `hatrpo_gru128` (5 steps each, no events inside their timed regions, fresh
+A plain run does only what the headline figure needs: build the runner, `--warmup` untimed steps, `--steps` timed steps,
+the outputs of the last timed step if `--dump-outputs DIR` is given, one JSON line (`metric`, `value`, `unit`,
+`higher_is_better`, `dtype`, `ms_per_step` = milliseconds per timed step).  Nothing is instrumented inside or around its timed
+region.  Everything below -- `roofline`, `kernels`, the measured shader clock, `cpu_baseline`, `other_configs` and, with
+N > 1 ranks, the `weak` figure -- is measured only with `--full`.
+
+`--dump-outputs DIR`: after the timed region, what the last timed step handed back or left behind for its caller, one
+`DIR/<name>.npy` each (float32 / float64): `returns` / `advantages` of compute(), the train infos of every agent and of
+the critic (`actor_info_<key>`, `critic_info_<key>`), every agent's parameters after the update (`actor_params_<a>`,
+reference order), the critic's (`critic_params`) and the ValueNorm statistics (`value_norm_stats`).  The inputs are
+seeded: the same arguments give the same inputs in every run.  At most 64 MB in all; a larger array would be replaced by a
+fixed, seeded sample of its flat elements (the same elements in every run).
+
+With `--full`, the default run (mpe) appends the three other BASELINE workloads and the coverage workload `hatrpo_gru128` (5 steps each, no events inside their timed regions, fresh
 runners, AFTER the headline region and the CPU baseline; each with its own bounded CPU baseline) to the same line as
 `other_configs` (`--no-other-configs` to skip).
 
-Prints ONE JSON line (rank 0).  `roofline`: the streaming kernel family with the largest total time per step (decided in the
+Prints ONE JSON line (rank 0).  With `--full`: `roofline`: the streaming kernel family with the largest total time per step (decided in the
 last warm-up step, where every family is bracketed by HIP events; inside the timed region only that family is) -- achieved =
 algorithmic HBM bytes of its launches in the timed region (harl_amd/traffic.py, from each launch's own arguments) / their
 HIP-event time; `traffic` = measured HBM bytes per launch from the committed PMC pass of that kernel
@@ -207,7 +220,7 @@ def build_gpu_runner(w: dict, n_local: int, rank: int, world: int, device, logp:
     return r
 
 
-def one_step(r) -> None:
+def one_step(r):
     # In training every step sees a freshly filled rollout buffer; the synthetic buffers here never change.  train()
     # itself drops the per-buffer caches (the normalised-input images, nets.invalidate_caches) on entry, so that work
     # stays inside every timed step; the explicit calls only cover compute()'s critic forward.
@@ -215,7 +228,41 @@ def one_step(r) -> None:
         a.actor.invalidate_caches()
     r.critic.critic.invalidate_caches()
     r.compute()
-    r.train()
+    return r.train()
+
+
+DUMP_LIMIT = 64 << 20  # bytes of all arrays `--dump-outputs` writes
+
+
+def dump_outputs(r, infos, out_dir: str) -> list:
+    """Write what the last step handed its caller (train()'s infos) or left in the runner for it (compute()'s returns and
+    advantages, the updated parameters, the ValueNorm statistics) as <out_dir>/<name>.npy.  An array above its share of
+    DUMP_LIMIT is replaced by a fixed, seeded sample of its flat elements (the same elements in every run)."""
+    actor_infos, critic_info = infos
+    arrs = {}
+    for k in sorted(set().union(*(d.keys() for d in actor_infos))):
+        arrs[f"actor_info_{k}"] = np.array([float(d.get(k, np.nan)) for d in actor_infos], dtype=np.float64)
+    for k in sorted(critic_info):
+        arrs[f"critic_info_{k}"] = np.array([float(critic_info[k])], dtype=np.float64)
+    cb = r.critic_buffer  # (the caller has synchronised the device)
+    arrs["returns"] = cb.returns.detach().cpu().numpy()
+    arrs["advantages"] = cb.advantages.detach().cpu().numpy()
+    for a, x in enumerate(r.actor):
+        arrs[f"actor_params_{a}"] = x.actor.flat_reference().cpu().numpy()
+    arrs["critic_params"] = r.critic.critic.flat_reference().cpu().numpy()
+    if r.value_normalizer is not None:
+        arrs["value_norm_stats"] = r.value_normalizer.stats.detach().cpu().numpy()
+    os.makedirs(out_dir, exist_ok=True)
+    share = DUMP_LIMIT // len(arrs)
+    for name, x in arrs.items():
+        if x.dtype not in (np.float32, np.float64):
+            x = x.astype(np.float64)
+        if x.nbytes > share:
+            n = max(1, share // x.itemsize)
+            idx = np.sort(np.random.default_rng(0).choice(x.size, size=n, replace=False))
+            x = np.ascontiguousarray(x.reshape(-1)[idx])
+        np.save(os.path.join(out_dir, f"{name}.npy"), x)
+    return sorted(arrs)
 
 
 def cpu_baseline(w: dict, n_cols: int, threads: int, reps: int = 3) -> dict:
@@ -274,7 +321,7 @@ def ranks_seen(comm, device) -> int:
 
 
 def measure(w: dict, cfg_name: str, args, comm, rank: int, world: int, device, n_local: int, steps: int, warmup: int,
-            instr_steps: int, scaling: str = "weak", region_events: bool = True):
+            instr_steps: int, scaling: str = "weak", region_events: bool = True, dump_dir: str | None = None):
     """Build the runner of one workload, warm up, time `steps` steps between barriers and collect the per-kernel figures.
     Returns the JSON record of this workload on rank 0 (None elsewhere).
     ``region_events`` = False (the workloads ATTACHED to the default line as `other_configs`): no HIP events inside the timed
@@ -285,6 +332,9 @@ def measure(w: dict, cfg_name: str, args, comm, rank: int, world: int, device, n
     from harl_amd import _lib
 
     Tn = w["T"]
+    # a plain run (no --full) times the steps and nothing else: no HIP events, no clock probe, no instrumented steps
+    timing = args.full and not args.no_kernel_timing
+    all_tags = args.full and args.time_all_tags
     r = build_gpu_runner(w, n_local, rank, world, device, args.logp)
 
     def barrier():
@@ -303,7 +353,7 @@ def measure(w: dict, cfg_name: str, args, comm, rank: int, world: int, device, n
                  "dw_trunk", "dw_gru")
     warm_kern = {}
     for k in range(warmup):
-        last = k == warmup - 1 and not args.no_kernel_timing and not args.time_all_tags
+        last = k == warmup - 1 and timing and not all_tags
         if last:  # (critic chain on the main stream for this step: per-launch durations without a second kernel sharing the chip)
             prev_cs = os.environ.get("HARL_CRITIC_STREAM")
             os.environ["HARL_CRITIC_STREAM"] = "0"
@@ -321,7 +371,7 @@ def measure(w: dict, cfg_name: str, args, comm, rank: int, world: int, device, n
     # against the constant 100 MHz counter while a whole step runs next to it (harl_clock_probe).  The matrix-pipe fractions
     # below are computed against this clock; the nominal 2.4 GHz figure stays next to them as `*_nominal`.
     clock_ghz = None
-    if not args.no_kernel_timing:
+    if timing:
         t_est = time.perf_counter()
         one_step(r)
         torch.cuda.synchronize()
@@ -340,27 +390,31 @@ def measure(w: dict, cfg_name: str, args, comm, rank: int, world: int, device, n
     cw = {k: v for k, v in warm_kern.items() if v["n"] > 0 and v.get("bytes")}
     if cw:
         region_tags = (max(cw, key=lambda k: cw[k]["total_ms"]),)
-    if not args.no_kernel_timing and region_events:
+    if timing and region_events:
         if cw:  # two events per bracketed launch, created before the clock starts
             _lib.reserve_timing_events(2 * (cw[region_tags[0]]["n"] + 8) * steps)
-        _lib.enable_kernel_timing(True, None if args.time_all_tags else region_tags)
+        _lib.enable_kernel_timing(True, None if all_tags else region_tags)
+    infos = None
     t0 = time.perf_counter()
     for _ in range(steps):
-        one_step(r)
+        infos = one_step(r)
     barrier()
     dt = time.perf_counter() - t0
     roof_kern = {}
-    if not args.no_kernel_timing and region_events:
+    if timing and region_events:
         roof_kern = _lib.collect_kernel_timing()
         _lib.enable_kernel_timing(False)
+    dumped = None
+    if dump_dir and rank == 0 and infos is not None:  # (before the instrumented steps below move the parameters on)
+        dumped = dump_outputs(r, infos, dump_dir)
     if comm.enabled:
         tt = torch.tensor([dt], dtype=torch.float64, device=device)
         torch.distributed.all_reduce(tt, op=torch.distributed.ReduceOp.MAX)
         dt = float(tt.item())
     # Full per-kernel breakdown (every tagged launch, ~10 % of wall time): `instr_steps` further steps of the SAME
     # workload after the timed region, so that it does not understate `value`.
-    kern = dict(roof_kern) if args.time_all_tags else {}
-    if not args.no_kernel_timing and instr_steps > 0:
+    kern = dict(roof_kern) if all_tags else {}
+    if timing and instr_steps > 0:
         # (ONE stream here: in the timed region the critic's update runs on a stream of its own next to the actors' chain,
         # so two kernels share the chip and every per-launch duration contains its neighbour's slices; the per-kernel table
         # and `roofline.single_stream` are taken with the critic chain back on the main stream)
@@ -445,7 +499,7 @@ def measure(w: dict, cfg_name: str, args, comm, rank: int, world: int, device, n
                     note="whole step per GPU against SURVEY.md 8(d)'s roofline (58.8 M transitions/s per GPU = 100 % of the dense "
                          "fp32-MFMA peak, 157.3 TFLOP/s); the GEMMs run on the bf16 pipe as six exact products")
             ks = kern.get(dom)
-            if ks and ks.get("bytes") and not args.time_all_tags:
+            if ks and ks.get("bytes") and not all_tags:
                 a1 = ks["bytes"] / (ks["total_ms"] * 1e-3)
                 roof["single_stream"] = dict(
                     achieved=a1 / 1e9, frac=a1 / HBM_PEAK, avg_ms=ks["avg_ms"], launches=ks["n"],
@@ -486,7 +540,7 @@ def measure(w: dict, cfg_name: str, args, comm, rank: int, world: int, device, n
         # own arguments, harl_amd/traffic.py ALGORITHMIC_FLOPS) -- the only end-to-end figure HATRPO has (CG / line-search
         # trip counts are data dependent); for HAPPO it is the closed form minus the pre-update pass shared with epoch 0
         ex = sum(v.get("flops") or 0.0 for v in kern.values())
-        if ex > 0 and instr_steps > 0 and not args.time_all_tags:
+        if ex > 0 and instr_steps > 0 and not all_tags:
             per_step = ex / instr_steps
             out.setdefault("end_to_end", {}).update(
                 executed_flops_per_step=per_step, executed_tflops=per_step / (dt / steps) / 1e12,
@@ -501,6 +555,12 @@ def measure(w: dict, cfg_name: str, args, comm, rank: int, world: int, device, n
                               "contract's figure (SURVEY.md 8d), not a statement that the step is nearly done")
             if roof is not None:
                 roof["bf16x6_end_to_end"] = out["end_to_end"]["bf16x6_frac_of_bf16_mfma_peak"]
+        if not args.full:  # a plain run measured none of these
+            for k in ("roofline", "kernels", "kernel_timing"):
+                out.pop(k)
+        if dumped is not None:
+            out["outputs"] = dict(dir=dump_dir, names=dumped,
+                                  note="the last timed step's outputs, one <name>.npy each (--dump-outputs)")
     return out
 
 
@@ -539,7 +599,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--config", choices=sorted(WORKLOADS), default="mpe")
     ap.add_argument("--scaling", choices=("auto", "weak", "strong"), default="auto",
-                    help="auto (default): one rank = the config's single-GPU size; N > 1 ranks = BOTH figures on the one line -- "
+                    help="auto (default): one rank = the config's single-GPU size; N > 1 ranks = BOTH figures on the one line (the weak one with --full) -- "
                          "headline `value` = STRONG scaling at the n_rollout_threads the BASELINE quotes the workload on (4096 "
                          "global for mpe, 8192 for cheetah6 = configs[2]; split over the ranks), and `weak` = the config's size on "
                          "every rank.  weak / strong: that one figure only")
@@ -549,6 +609,12 @@ def main():
     ap.add_argument("--logp", choices=("recipe", "onpolicy"), default="recipe",
                     help="stored log-probs: SURVEY 8d recipe (default) or on-policy (ratios ~ 1)")
     ap.add_argument("--dist-single", action="store_true", help="initialise the nccl (RCCL) group even with one rank")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: roofline / per-kernel figures and the measured "
+                         "shader clock (HIP events, extra steps), the CPU baseline, `other_configs` and, with N > 1 ranks, the "
+                         "`weak` figure.  The options below up to --other-cpu-cols only act with --full")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step as DIR/<name>.npy (float32 / float64, at most 64 MB in all)")
     ap.add_argument("--cpu-cols", type=int, default=-1, help="rollout threads of the bounded CPU-baseline sample (0 = skip, -1 = auto)")
     ap.add_argument("--cpu-reps", type=int, default=3, help="timed CPU-baseline updates after the warm-up one (best of)")
     ap.add_argument("--cpu-threads", type=int, default=16,
@@ -575,12 +641,12 @@ def main():
         rc = subprocess.call([sys.executable, os.path.abspath(__file__)] + base)
         keep = []
         skip = False
-        for a in base:  # drop the first run's workload selection
+        for a in base:  # drop the first run's workload selection (and its output directory: the dumps are the first line's)
             if skip:
                 skip = False
-            elif a in ("--config", "--scaling", "--global-threads", "--threads-per-gpu"):
+            elif a in ("--config", "--scaling", "--global-threads", "--threads-per-gpu", "--dump-outputs"):
                 skip = True
-            elif not a.startswith(("--config=", "--scaling=", "--global-threads=", "--threads-per-gpu=")):
+            elif not a.startswith(("--config=", "--scaling=", "--global-threads=", "--threads-per-gpu=", "--dump-outputs=")):
                 keep.append(a)
         rc2 = subprocess.call([sys.executable, os.path.abspath(__file__)] + keep +
                               ["--config", "cheetah6", "--scaling", "strong", "--global-threads", "8192"])  # = configs[2] as quoted
@@ -600,15 +666,16 @@ def main():
     if args.dist_single and "RANK" not in os.environ:  # a one-rank RCCL group: exercises the collective branch on a 1-GPU box
         os.environ.update(RANK="0", LOCAL_RANK="0", WORLD_SIZE="1", MASTER_ADDR="127.0.0.1",
                           MASTER_PORT=os.environ.get("MASTER_PORT", "29533"), HARL_DIST_SINGLE="1")
-    comm = init_from_env()
+    comm = init_from_env("gloo" if args.dry_run else None)  # (the dry run's rendezvous: gloo, also where a GPU is visible)
     rank, world = comm.rank, comm.world_size
     if args.dry_run:  # tests/test_bench_launcher_cpu.py: the command line the driver runs, minus the GPU work
         t = torch.tensor([float(rank + 1), 1.0], dtype=torch.float64)
         comm.all_reduce_sum(t)
         assert world == args.gpus and float(t[0].item()) == world * (world + 1) / 2, (world, args.gpus, t)
         g_threads = args.global_threads or BASELINE_GLOBAL_THREADS.get(args.config, w["N"])
-        both = args.scaling == "auto" and world > 1 and not args.threads_per_gpu
-        strong = args.scaling == "strong" or both
+        auto_strong = args.scaling == "auto" and world > 1 and not args.threads_per_gpu
+        both = auto_strong and args.full
+        strong = args.scaling == "strong" or auto_strong
         if rank == 0:
             os.write(json_fd, (json.dumps(dict(metric=w["metric"], value=None, unit="transitions/s", n_gpus=world, steps=args.steps,
                                                warmup=args.warmup, dry_run=True, scaling="strong" if strong else "weak",
@@ -627,8 +694,9 @@ def main():
     torch.cuda.set_device(device)
     assert world == args.gpus or (world == 1 and args.gpus == 1), f"launched {world} ranks for --gpus {args.gpus}"
     g_threads = args.global_threads or BASELINE_GLOBAL_THREADS.get(args.config, w["N"])
-    both = args.scaling == "auto" and world > 1 and not args.threads_per_gpu
-    scaling = "strong" if (args.scaling == "strong" or both) else "weak"
+    auto_strong = args.scaling == "auto" and world > 1 and not args.threads_per_gpu
+    both = auto_strong and args.full  # (the weak figure next to the strong headline: --full only)
+    scaling = "strong" if (args.scaling == "strong" or auto_strong) else "weak"
     if scaling == "strong":
         assert g_threads % world == 0, "--global-threads must be divisible by the number of ranks"
         n_local = g_threads // world
@@ -636,7 +704,8 @@ def main():
         n_local = args.threads_per_gpu or w["N"]
     Tn = w["T"]
 
-    out = measure(w, args.config, args, comm, rank, world, device, n_local, args.steps, args.warmup, args.instr_steps, scaling)
+    out = measure(w, args.config, args, comm, rank, world, device, n_local, args.steps, args.warmup,
+                  args.instr_steps if args.full else 0, scaling, dump_dir=args.dump_outputs)
     if both:
         # the weak-scaling figure of the same job on the same line (every rank at the config's single-GPU size): its own
         # barrier-bracketed region of the same number of steps, after the headline region
@@ -649,7 +718,7 @@ def main():
             out["strong"] = dict(value=out["value"], ms_per_step=out["ms_per_step"], scaling="strong",
                                  n_rollout_threads_per_gpu=n_local, n_rollout_threads_global=g_threads,
                                  note="headline `value`: the BASELINE's global n_rollout_threads split over the ranks")
-    if rank == 0:
+    if rank == 0 and args.full:
         cols = args.cpu_cols
         if cols < 0:  # ~10-30 s of CPU work per update for every configuration
             cols = {"mpe": 512, "cheetah6": 512, "smac3s5z": 128, "humanoid17": 64, "hatrpo_gru128": 64}[w.get("base", args.config)]
@@ -659,7 +728,7 @@ def main():
     # baseline, fresh runner each, a few steps): `--config <name>` gives the full record of any one of them
     # (single-process runs only: the scaling runs time the headline workload, and an attached workload that failed on ONE rank
     # would leave the others waiting in a collective)
-    if args.other_configs and world == 1 and args.config == "mpe" and scaling == "weak" and not args.threads_per_gpu:
+    if args.full and args.other_configs and world == 1 and args.config == "mpe" and scaling == "weak" and not args.threads_per_gpu:
         others = {}
         for name in ("cheetah6", "smac3s5z", "smac3s5z_n4096", "humanoid17", "humanoid17_n4096", "hatrpo_gru128"):
             torch.cuda.empty_cache()

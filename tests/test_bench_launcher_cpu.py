@@ -22,13 +22,19 @@ def _run(cmd):
 
 @pytest.mark.parametrize("n", [2, 4])
 def test_bench_self_spawns_ranks(n):
-    out = _run([sys.executable, "bench.py", "--gpus", str(n), "--steps", "1", "--warmup", "0", "--dry-run"])
+    out = _run([sys.executable, "bench.py", "--gpus", str(n), "--steps", "1", "--warmup", "0", "--dry-run", "--full"])
     assert out["n_gpus"] == n and out["config"]["parallelism"] == f"dp{n}" and out["config"]["collective"] == "gloo"
     # the multi-GPU line answers the BASELINE's question: headline = strong scaling at the BASELINE's
     # global n_rollout_threads, the weak figure on the same line, and the rank count as the communicator itself reports it
     assert out["scaling"] == "strong" and out["config"]["n_rollout_threads_global"] == 4096
     assert out["config"]["n_rollout_threads_per_gpu"] == 4096 // n and out["config"]["ranks_seen"] == n
     assert out["weak"]["n_rollout_threads_global"] == 4096 * n
+
+
+def test_bench_plain_multi_rank_times_the_headline_only():
+    """Without --full the multi-rank line carries the strong-scaling headline alone: no `weak` region is timed."""
+    out = _run([sys.executable, "bench.py", "--gpus", "2", "--steps", "1", "--warmup", "0", "--dry-run"])
+    assert out["scaling"] == "strong" and out["config"]["n_rollout_threads_global"] == 4096 and out["weak"] is None
 
 
 def test_bench_strong_size_of_cheetah6_is_configs2():

@@ -143,8 +143,10 @@ def _oneshot_cpu_worker(rank, world, port, q):
         dist.destroy_process_group()
 
 
-def test_oneshot_request_without_gpu_falls_back_to_the_backend():
+def test_oneshot_request_without_gpu_falls_back_to_the_backend(monkeypatch):
     world, port = 2, _free_port()
+    for var in ("HIP_VISIBLE_DEVICES", "CUDA_VISIBLE_DEVICES"):  # the workers see no GPU, also on a GPU box
+        monkeypatch.setenv(var, "")
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
     procs = [ctx.Process(target=_oneshot_cpu_worker, args=(r, world, port, q)) for r in range(world)]
