@@ -31,11 +31,13 @@ static __device__ long long harl_phase_wg[8][256][3];
     _pt_last = _t;                                       \
     __builtin_amdgcn_sched_barrier(0);                   \
   } while (0)
-#define PHASE_END(slot)                                  \
+#define PHASE_END(slot) PHASE_END_BY(slot, 0)
+// ... recorded by thread `tid` (its wave's sums: kernels whose waves take different roles)
+#define PHASE_END_BY(slot, tid)                          \
   do {                                                   \
-    if (blockIdx.x == 0 && threadIdx.x == 0)             \
+    if (blockIdx.x == 0 && threadIdx.x == (tid))         \
       for (int _k = 0; _k < HARL_NPHASE; ++_k) harl_phase_cyc[slot][_k] = _pt_acc[_k]; \
-    if (threadIdx.x == 0 && blockIdx.x < 256) {          \
+    if (threadIdx.x == (tid) && blockIdx.x < 256) {      \
       harl_phase_wg[slot][blockIdx.x][0] = __builtin_readcyclecounter() - _pt_c0; \
       harl_phase_wg[slot][blockIdx.x][1] = _pt_rt0;      \
       harl_phase_wg[slot][blockIdx.x][2] = __builtin_amdgcn_s_memrealtime(); \
@@ -52,6 +54,7 @@ static __device__ long long harl_phase_wg[8][256][3];
 #define PHASE_BEGIN()
 #define PHASE(i)
 #define PHASE_END(slot)
+#define PHASE_END_BY(slot, tid)
 #define HARL_PHASE_ACCESSOR(tu)
 #endif
 

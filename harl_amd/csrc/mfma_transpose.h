@@ -110,8 +110,9 @@ __device__ __forceinline__ void dw_tile(f32x16 &acc, const u32x4 (&A)[3][2], con
 
 // Combine the four waves' weight-gradient accumulators acc[MT_][NT_] (+ per-lane bias sums db[MT_]) through LDS in fixed
 // order and write ONE partial row  dWp[32 MT_][KP] | dbp[32 MT_]  (the layout harl_reduce_partials_multi expects);
-// rows gridDim.x .. n_part_rows-1 of the arena are cleared (this launch runs at most one workgroup per CU).
-template <int MT_, int NT_>
+// rows gridDim.x .. n_part_rows-1 of the arena are cleared (this launch runs at most one workgroup per CU).  NTHR: the
+// workgroup's threads; waves 4.. (if any) only take part in the barriers and the copy.
+template <int MT_, int NT_, int NTHR = WG_THREADS>
 __device__ __forceinline__ void finish_partials(f32x16 (&acc)[MT_][NT_], float (&db)[MT_], float *buf,
                                                 float *__restrict__ part, int n_part_rows) {
   constexpr int HO = 32 * MT_, KP = 32 * NT_, ROW = HO * KP + HO;
@@ -141,10 +142,10 @@ __device__ __forceinline__ void finish_partials(f32x16 (&acc)[MT_][NT_], float (
     __syncthreads();
   }
   float *out = part + (long)blockIdx.x * ROW;
-  for (int e = threadIdx.x; e < ROW; e += WG_THREADS) out[e] = buf[e];
+  for (int e = threadIdx.x; e < ROW; e += NTHR) out[e] = buf[e];
   for (int row = blockIdx.x + gridDim.x; row < n_part_rows; row += gridDim.x) {
     float *z = part + (long)row * ROW;
-    for (int e = threadIdx.x; e < ROW; e += WG_THREADS) z[e] = 0.f;
+    for (int e = threadIdx.x; e < ROW; e += NTHR) z[e] = 0.f;
   }
 }
 

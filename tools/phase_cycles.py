@@ -23,6 +23,10 @@ NAMES = {
     ("mlp", 1): ("k_bwd_dx<KT=0>", ["split dz", "issue loads", "GEMM", "LN bwd + store"]),
     ("mlp", 3): ("k_bwd_dx_dw (bwd_full[_dw1]: dx + dW' + dW1' in one launch)",
                  ["issue loads", "GEMM dx", "LN bwd (+ store)", "dW1", "D-part loads issue", "barrier", "MFMA rounds + fillers", "B stores"]),
+    ("mlp", 4): ("k_bwd_dx_dw8 owner (wave 0; the barriers it meets inside the GEMM count there)",
+                 ["loads + split + barrier 0", "GEMM dx (+ barriers 1..2)", "LN bwd (+ store)", "dW1"]),
+    ("mlp", 5): ("k_bwd_dx_dw8 gradient wave (wave 4)",
+                 ["-", "-", "-", "-", "D-part loads issue", "barrier", "MFMA rounds + fillers", "B stores"]),
     ("mlp", 2): ("k_dw_tr", ["barrier 1", "split + store", "barrier 2", "MFMA phase"]),
     ("wide", 0): ("k_fwd_fused2x", ["split x0n + load", "GEMM 1", "relu/LN 1 + store", "split x1", "GEMM 2", "relu/LN 2 + store"]),
     ("heads", 0): ("k_actor_head<TRAIN, FUSE>", ["row loads + x load issue", "head fwd", "sample / loss", "head dW", "head bwd + store"]),
