@@ -1314,812 +1314,7 @@ __global__ __launch_bounds__(64 * G6_WAVES, 1) void k_dw_gru6(DwGru6 P, long n_s
   }
 }
 
-// =============================================================================================
-// k_bwd_dx_dw: the WHOLE backward of one hidden Linear(128 -> 128) and the relu + LayerNorm in front of it in ONE persistent
-// launch (round 5): dz_prev = LNrelu'(Wp^T dz), dW' += dz^T x_hat_prev, db' += sum dz, and -- first-layer variant, KT = 1 --
-// dW_1' += dz_1^T x0n.  It replaces the pair harl_mlp_dw_partials(dz, x_hat_prev) + harl_mlp_bwd_dx(...), which streamed the same
-// two operands (dz 512 B + x_hat_prev 512 B per sample) from HBM one after the other: half of the MPE step's time and 17 of its
-// 58 GB.  Matches autograd through MLPLayer (harl/models/base/mlp.py:25-38, happo.py:93-100).
-//
-// One workgroup per CU, four waves, 144 KiB of LDS: the three split images of Wp^T (96 KiB, as k_bwd_dx) and TWO transposition
-// buffers for x_hat_prev^T (k_dw_tr's image, 24 KiB each).  A super-round = four slabs, one per wave:
-//   O part (the owner's slab, k_bwd_dx's body): dz already split (below) -> 192 MFMAs -> LayerNorm/ReLU backward -> dz_prev
-//     (stored, KT = 0) or the first-layer weight gradient on the matrix-pipe transposes (KT = 1, mfma_transpose.h);
-//   D part, four rounds, one per slab of the super-round: wave w owns row tile w of dW' (output features 32 w .. 32 w + 31).
-//     Its A operand -- that 32-feature block of the slab's dz, transposed -- it makes itself on the matrix pipe (its four float4
-//     pieces of the block, split exactly, times the permuted identity: 6 MFMAs, no LDS, and the transposition's row sums are
-//     db'); the B operand x_hat_prev^T is shared: every wave splits a quarter of the slab's pieces and stores them into the
-//     round's buffer, the fragments come back through ds_read_b64_tr_b16.  Both are fetched a second time microseconds after
-//     their owners touched them -- which, measured (rocprofv3 --pmc FETCH_SIZE, profiles/r05_hbm_traffic.md), does NOT stay in the
-//     L2: 1.56 GB leave it per launch against 0.96 GB of operands (a super-round's working set per XCD, 32 workgroups x 4 slabs x
-//     32 KB, is the L2's 4 MB); the pair of layer kernels fetched 1.83 GB.
-// Version 1 of this kernel (one buffer, both operands through LDS, two barriers per round) measured no faster than the pair it
-// replaces: with one workgroup per CU nothing overlaps a barrier wait (profiles/r05_bwd_fused_ab.md).  Hence the software
-// pipeline: everything round n+1 needs is prepared DURING round n's 48 product MFMAs -- a wave has one MFMA in flight for 32
-// cycles but needs ~12 of issue for it, and up to five VALU instructions placed BETWEEN two MFMAs are free
-// (profiles/r03_mfma_valu_overlap.md) -- as filler chunks of 5-8 VALU pinned behind each MFMA with sched_barrier (source order
-// is honoured exactly): the split of the next A block (16 chunks), its 6 transposing MFMAs, the packing of their results, the
-// split of the next B pieces (16 chunks), and a share of the split of the OWNER's next slab of dz (64 chunks per super-round:
-// the 2.2k cycles k_bwd_dx spends in "split dz" per slab).  The B terms are stored at the END of round n into the buffer round
-// n-1 read, so ONE barrier per round suffices (every wave has left round n-1 when any wave stores for n+1), and it finds the
-// stores long complete.  FILL = false runs the same chunks as a block in front of the product MFMAs (A/B).
-// Per-workgroup partial rows in the layout of harl_reduce_partials_multi: dW' by tiles straight from the accumulators (the
-// waves own disjoint row tiles), dW_1' through finish_partials; rows gridDim.x .. n_part_rows-1 of both arenas are cleared.
-// =============================================================================================
-__device__ __forceinline__ void split_stage1(float f0, float f1, unsigned &p1, float &r0, float &r1) {
-  const unsigned b0 = __float_as_uint(f0), b1 = __float_as_uint(f1);
-  p1 = __builtin_amdgcn_perm(b1, b0, 0x07060302u);
-  r0 = f0 - __uint_as_float(b0 & 0xffff0000u);
-  r1 = f1 - __uint_as_float(b1 & 0xffff0000u);
-}
-__device__ __forceinline__ void split_stage2(float r0, float r1, unsigned &p2, unsigned &p3) {
-  const unsigned c0 = __float_as_uint(r0), c1 = __float_as_uint(r1);
-  p2 = __builtin_amdgcn_perm(c1, c0, 0x07060302u);
-  const float q0 = r0 - __uint_as_float(c0 & 0xffff0000u), q1 = r1 - __uint_as_float(c1 & 0xffff0000u);
-  p3 = __builtin_amdgcn_perm(__float_as_uint(q1), __float_as_uint(q0), 0x07060302u);
-}
-
-// compile-time loop: f(std::integral_constant<int, I>) for I = I0 .. N-1 -- every index inside is a constant expression, whatever
-// the unroller thinks of the body's size (a `#pragma unroll` loop that stays rolled turns register arrays into scratch)
-template <int I, int N, typename F>
-__device__ __forceinline__ void static_for(F &&f) {
-  if constexpr (I < N) {
-    f(std::integral_constant<int, I>{});
-    static_for<I + 1, N>(f);
-  }
-}
-
-constexpr int BDW_SQ = (128 / 16) * 128 + 8, BDW_IMG = 8 * BDW_SQ;  // k_dw_tr's image geometry at H = 128
-constexpr int BDW_BUF = 3 * BDW_IMG;                                // one transposition buffer: three term images
-constexpr size_t bdw_lds_bytes() { return split_image_bytes(128, 128) + (size_t)2 * BDW_BUF; }
-
-#ifndef HARL_BWD_OSPLIT_IN_GEMM
-#define HARL_BWD_OSPLIT_IN_GEMM 1
-#endif
-constexpr bool OSPLIT_IN_GEMM = HARL_BWD_OSPLIT_IN_GEMM != 0;  // (0: the owner's split in the weight-gradient rounds, rounds 5 - 6; A/B builds)
-template <int KT, bool FILL>
-__global__ __launch_bounds__(WG_THREADS, 1) void k_bwd_dx_dw(
-    const float *__restrict__ dz, const float *__restrict__ xprev, const uint32_t *__restrict__ mask_prev,
-    const float *__restrict__ rstd_prev, const float *__restrict__ Wp, float *__restrict__ dz_prev, long n_slabs,
-    const float *__restrict__ x0n, float *__restrict__ dw1_part, float *__restrict__ dw2_part, int n_part_rows) {
-  constexpr int H = 128, MT = 4, NJ = 8, NR = 64, KPF = 32;
-  extern __shared__ __attribute__((aligned(16))) float lds[];
-  PHASE_BEGIN();
-  u32x4 *img = reinterpret_cast<u32x4 *>(lds);
-  unsigned char *Bb = reinterpret_cast<unsigned char *>(img + 3 * MT * NJ * 64);  // [2][3 terms][BDW_IMG]: x_hat_prev^T staging
-  stage_split_matrix<H, H, true, WG_THREADS>(img, Wp);
-  __syncthreads();
-  const int lane = threadIdx.x & 63, wave = wave_id();
-  const int i = lane & 31, h = lane >> 5;
-  const u32x4 *wl = img + lane;
-  const long sr_stride = (long)gridDim.x * WAVES_PER_WG;
-  const long base0 = (long)blockIdx.x * WAVES_PER_WG;
-  const Ident ident = make_ident(lane);
-
-  // ---- persistent accumulators
-  f32x16 acc2[4];                 // dW' tiles (row tile = wave, column tiles 0..3)
-  f32x16 acc1[KT > 0 ? 4 : 1];    // dW_1' tiles (KT = 1)
-  float dbs[KT > 0 ? 4 : 1];      // db_1' (per-lane sums over the lane's samples)
-  float db2 = 0.f;                // db' of feature 32 wave + (lane & 31): this lane half's 16 samples of every slab
-#pragma unroll
-  for (int b = 0; b < 4; ++b)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc2[b][r] = 0.f;
-#pragma unroll
-  for (int a = 0; a < (KT > 0 ? 4 : 1); ++a) {
-    dbs[a] = 0.f;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc1[a][r] = 0.f;
-  }
-
-  // ---- D-part state.  prA: the four float4 pieces 4 wave + u of a slab's dz = registers 16 wave .. 16 wave + 15 of the
-  // accumulator layout = the 32-feature block `wave`; prB: pieces 4 wave + u of x_hat_prev (this wave's quarter of the B operand)
-  f32x4 prA[4], prB[4];
-  u32x2_t spB[4][3];          // split terms of prB: one ds_write_b64 each
-  u32x4 ya[3][2];             // split terms of prA by k-step (split_transpose_block's y1 / y2 / y3)
-  f32x16 tc[3];               // the three transposed terms (lane = feature, 16 samples)
-  u32x4 At[3][2], AtN[3][2];  // A operands [term][k-step] of this round / of the next one
-  float rr0 = 0.f, rr1 = 0.f; // remainders between the two stages of a pair's split
-  auto d_load = [&](long ds) {
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      prA[u] = (reinterpret_cast<const f32x4 *>(dz + ds * (long)(H * SLAB)) + lane)[(4 * wave + u) * WAVE];
-      prB[u] = (reinterpret_cast<const f32x4 *>(xprev + ds * (long)(H * SLAB)) + lane)[(4 * wave + u) * WAVE];
-    }
-  };
-  // Preparing a round that will not be executed (past the last slab) is harmless -- its operands are never multiplied -- except
-  // for the bias sums of its A block: `vnext` (1 or 0) multiplies them.  The loads of such a round are clamped to a valid slab.
-  float vnext = 1.f;
-  auto d_load_next = [&](long ds, long fallback) { d_load(ds < n_slabs ? ds : fallback); };
-  // A chunk k (0..15): pair p = k >> 1 = registers 2p, 2p + 1 of the block -> word p & 3 of k-step p >> 2; stage k & 1
-  auto a_chunk = [&](int k) {
-    const int pi = k >> 1, j = pi >> 2, c = pi & 3, u = pi >> 1, e = 2 * (pi & 1);
-    if ((k & 1) == 0) {
-      unsigned p1;
-      split_stage1(prA[u][e], prA[u][e + 1], p1, rr0, rr1);
-      ya[0][j][c] = p1;
-    } else {
-      unsigned p2, p3;
-      split_stage2(rr0, rr1, p2, p3);
-      ya[1][j][c] = p2;
-      ya[2][j][c] = p3;
-    }
-  };
-  // B chunk k (0..15): piece k >> 2, pair (k >> 1) & 1, stage k & 1
-  auto b_chunk = [&](int k) {
-    const int u = k >> 2, c2 = (k >> 1) & 1;
-    if ((k & 1) == 0) {
-      unsigned p1;
-      split_stage1(prB[u][2 * c2], prB[u][2 * c2 + 1], p1, rr0, rr1);
-      spB[u][0][c2] = p1;
-    } else {
-      unsigned p2, p3;
-      split_stage2(rr0, rr1, p2, p3);
-      spB[u][1][c2] = p2;
-      spB[u][2][c2] = p3;
-    }
-  };
-  // transposing MFMA k (0..5) of the A block: term k % 3, k-step k / 3 (mfma_transpose.h, transpose_block)
-  auto t_mfma = [&](int k) {
-    const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    const int t = k % 3;
-    if (k < 3) tc[t] = mfma_bf16(ya[t][0], ident.j0, zero);
-    else tc[t] = mfma_bf16(ya[t][1], ident.j1, tc[t]);
-  };
-  // pack chunk k (0..5): k < 3: term k -> the two k-step operands; k >= 3: its row sums into db'
-  auto p_chunk = [&](int k) {
-    if (k < 3) {
-      pack_transposed(tc[k], AtN[k][0], AtN[k][1]);
-    } else {
-      f32x2 a = {0.f, 0.f};
-#pragma unroll
-      for (int r = 0; r < 8; ++r) a += f32x2{tc[k - 3][2 * r], tc[k - 3][2 * r + 1]};
-      db2 += vnext * (a[0] + a[1]);
-    }
-  };
-  auto b_store = [&](int buf) {
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const int q = 4 * wave + u;
-      unsigned char *d = Bb + buf * BDW_BUF + (i >> 2) * BDW_SQ + (2 * (q >> 2) + ((q & 3) >> 1)) * 128 + (i & 3) * 32 +
-                         (8 * (q & 1) + 4 * h) * 2;
-#pragma unroll
-      for (int term = 0; term < 3; ++term) *reinterpret_cast<u32x2_t *>(d + term * BDW_IMG) = spB[u][term];
-    }
-  };
-  // B fragment of column tile `tile`, k-step ks: the eight samples sigma(r, h) = (r & 3) + 8 (r >> 2) + 4 h + 16 ks, r = 0..7 --
-  // the order the matrix-pipe transposition leaves the A operand in (mfma_transpose.h): sample quads 4 ks + h and 4 ks + 2 + h
-  const int p16 = lane & 15, g1b = (lane >> 4) & 1;
-  const int frag_lane = g1b * 128 + (p16 >> 2) * 32 + (p16 & 3) * 8;
-  auto read_frag = [&](int buf, int ks, int tile, u32x4 (&f)[3]) {
-#pragma unroll
-    for (int term = 0; term < 3; ++term) {
-      const unsigned char *fp = Bb + buf * BDW_BUF + term * BDW_IMG + (4 * ks + h) * BDW_SQ + 2 * tile * 128 + frag_lane;
-      const u32x2_t lo = tr_read(fp), hi = tr_read(fp + 2 * BDW_SQ);
-      f[term] = u32x4{lo[0], lo[1], hi[0], hi[1]};
-    }
-  };
-
-  // ---- owner state: the current slab's dz split into the B operands of the GEMM, the next slab's raw dz
-  float raw[NR];
-  u32x4 g1[NJ], g2[NJ], g3[NJ];
-  {
-    const long s0 = base0 + wave;
-    atl_load<H>(dz, s0 < n_slabs ? s0 : 0, lane, raw);
-    if constexpr (!OSPLIT_IN_GEMM) split_acts<NR, false>(raw, g1, g2, g3);
-  }
-  // O chunk k (0..63) of the NEXT slab's split: pair k>>1 (registers 2p, 2p+1 -> word p&3 of k-step p>>2), stage k&1
-  // (two streams of them run side by side in a round: each keeps its own remainders between the stages of a pair)
-  float rx0 = 0.f, rx1 = 0.f;
-  auto o_chunk = [&](int k, bool second_stream) {
-    const int pi = k >> 1, j = pi >> 2, c = pi & 3;
-    float &q0 = second_stream ? rx0 : rr0, &q1 = second_stream ? rx1 : rr1;
-    if ((k & 1) == 0) {
-      unsigned p1;
-      split_stage1(raw[2 * pi], raw[2 * pi + 1], p1, q0, q1);
-      g1[j][c] = p1;
-    } else {
-      unsigned p2, p3;
-      split_stage2(q0, q1, p2, p3);
-      g2[j][c] = p2;
-      g3[j][c] = p3;
-    }
-  };
-  if constexpr (OSPLIT_IN_GEMM) {  // k-step 0 of the first slab (later slabs: the last weight-gradient round's slots 32..39)
-#pragma unroll
-    for (int k = 0; k < 8; ++k) o_chunk(k, false);
-  }
-  // ---- the first round of the first super-round is prepared in the open
-  if (base0 < n_slabs) {
-    d_load(base0);
-#pragma unroll
-    for (int k = 0; k < 16; ++k) a_chunk(k);
-#pragma unroll
-    for (int k = 0; k < 6; ++k) t_mfma(k);
-#pragma unroll
-    for (int k = 0; k < 16; ++k) b_chunk(k);
-#pragma unroll
-    for (int k = 0; k < 6; ++k) p_chunk(k);
-#pragma unroll
-    for (int t = 0; t < 3; ++t) {
-      At[t][0] = AtN[t][0];
-      At[t][1] = AtN[t][1];
-    }
-    b_store(0);
-  }
-  PHASE(10);
-
-  for (long base = base0; base < n_slabs; base += sr_stride) {
-    const long slab = base + wave;
-    const bool own = slab < n_slabs;
-    const long nxt = slab + sr_stride < n_slabs ? slab + sr_stride : (own ? slab : 0);
-    // =========================== O part: this wave's own slab ===========================
-    if (own) {
-      float xh[NR];
-      atl_load<H>(xprev, slab, lane, xh);
-      const float rstd = rstd_prev[slab * SLAB + i];
-      uint32_t mbits[2];
-#pragma unroll
-      for (int w = 0; w < 2; ++w) mbits[w] = mask_prev[(slab * 2 + w) * WAVE + lane];
-      f32x4 x0r[KT > 0 ? KPF / 8 : 1];
-      if constexpr (KT > 0) {
-        const f32x4 *bp = reinterpret_cast<const f32x4 *>(x0n + slab * (long)(KPF * SLAB)) + lane;
-#pragma unroll
-        for (int q = 0; q < KPF / 8; ++q) x0r[q] = bp[q * WAVE];
-      }
-      f32x16 acc[MT];
-#pragma unroll
-      for (int t = 0; t < MT; ++t)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
-      PHASE(0);
-      if constexpr (OSPLIT_IN_GEMM) {
-        // the split of k-step j + 1 of THIS slab's dz (raw) behind the 24 product MFMAs of k-step j: one chunk (one stage of
-        // a pair: ~5.5 VALU) behind every third MFMA -- the 192 shadows of this GEMM were empty while the weight-gradient rounds carried
-        // 6.7 VALU per MFMA (profiles/r05_bwd_fused_ab.md), 64 of their 216 chunks being exactly these
-        split_gemm_fill<MT, NJ>(wl, g1, g2, g3, acc, [&](int s_, int k6) {
-          const int j1 = s_ / MT + 1, q = (s_ % MT) * 6 + k6;  // q = 0..23: the MFMA's position inside k-step j
-          if (j1 < NJ && q % 3 == 0) o_chunk(8 * j1 + q / 3, false);
-        });
-      } else {
-        split_gemm<MT, NJ>(wl, g1, g2, g3, acc, [](int) {});
-      }
-      PHASE(1);
-      float dx[NR];
-#pragma unroll
-      for (int R = 0; R < NR; ++R) dx[R] = acc[R >> 4][R & 15];
-      float out[NR];
-      ln_bwd_relu_mbits<H>(dx, xh, mbits, rstd, out);
-      if (dz_prev) atl_store<H>(dz_prev, slab, lane, out);
-      PHASE(2);
-      if constexpr (KT > 0) {
-        float xr0[KPF / 2];
-#pragma unroll
-        for (int q = 0; q < KPF / 8; ++q) {
-          xr0[4 * q + 0] = x0r[q][0];
-          xr0[4 * q + 1] = x0r[q][1];
-          xr0[4 * q + 2] = x0r[q][2];
-          xr0[4 * q + 3] = x0r[q][3];
-        }
-        u32x4 a1[KPF / 16], a2[KPF / 16], a3[KPF / 16];
-        split_acts<KPF / 2>(xr0, a1, a2, a3);
-        u32x4 Bt[3][2];
-        transpose_block<false>(a1[0], a1[1], a2[0], a2[1], a3[0], a3[1], ident, Bt);
-#pragma unroll
-        for (int a = 0; a < 4; ++a) {
-          u32x4 A1[3][2];
-          dbs[a] += split_transpose_block<true>(&out[16 * a], ident, A1);
-          dw_tile(acc1[a], A1, Bt);
-        }
-        PHASE(3);
-      }
-    }
-    // =========================== D part: the four slabs of this super-round ===========================
-    // the owner's NEXT slab of dz (g1..g3 are dead since the GEMM; first needed by the fillers of round 1) and this wave's
-    // pieces of round 1 (round 0's operands were prepared by the previous super-round's last round / the prologue) -- not
-    // earlier: the first-layer gradient above is the register peak of this kernel
-    atl_load<H>(dz, nxt, lane, raw);
-    d_load_next(base + 1, base);
-    PHASE(4);
-    static_for<0, 4>([&](auto rc) {
-      constexpr int r = decltype(rc)::value;
-      if (base + r < n_slabs) {  // workgroup-uniform
-        __syncthreads();  // every wave's B terms of this round are in buffer r & 1; buffer (r + 1) & 1 is free
-        PHASE(5);
-        // the round being prepared (r + 1, or round 0 of the next super-round) and the one whose pieces are requested (r + 2; none
-        // from round 3: the next super-round fetches its round 1 itself)
-        const long ds1 = r < 3 ? base + r + 1 : base + sr_stride;
-        const long ds2 = r < 2 ? base + r + 2 : base + sr_stride;
-        vnext = uniform_f(ds1 < n_slabs ? 1.f : 0.f);
-        // the owner's 64 split chunks: 0 / 22 / 22 / 20 per round, as a main stream of 16 (slots 32..47) and a second stream of
-        // 6 / 6 / 4 beside it (slots 32..); every range starts at an even chunk = the first stage of a pair
-        constexpr int O_FIRST = r == 1 ? 0 : (r == 2 ? 22 : 44), O_EXTRA = r == 3 ? 4 : 6;
-        // TSLOT: the product MFMA behind which the six transposing MFMAs are issued
-        constexpr int TSLOT = r == 0 ? 31 : 15;
-        auto slot = [&](auto sc) {  // filler work behind product MFMA s (0..47)
-          constexpr int s_ = decltype(sc)::value;
-          if constexpr (r == 0) {  // the pieces of round 1 were requested just above: nothing in the first 16 slots
-            if constexpr (s_ >= 16 && s_ < 32) a_chunk(s_ - 16);
-            else if constexpr (s_ >= 32 && s_ < 42) b_chunk(s_ - 32 + 6);
-            else if constexpr (s_ >= 42) p_chunk(s_ - 42);
-            if constexpr (s_ == 41) d_load_next(ds2, base);
-          } else {
-            if constexpr (s_ < 16) a_chunk(s_);
-            else if constexpr (s_ < 26) b_chunk(s_ - 16 + 6);
-            else if constexpr (s_ < 32) p_chunk(s_ - 26);
-            else if constexpr (!OSPLIT_IN_GEMM) {
-              o_chunk(O_FIRST + s_ - 32, false);
-              if constexpr (s_ - 32 < O_EXTRA) o_chunk(O_FIRST + 16 + s_ - 32, true);
-            } else if constexpr (r == 3 && s_ < 40) {
-              o_chunk(s_ - 32, false);  // k-step 0 of the owner's next slab; the other seven ride inside its dX GEMM
-            }
-            if constexpr (s_ == 25 && r < 3) d_load_next(ds2, base);
-          }
-          if constexpr (s_ == TSLOT) {  // the six transposing MFMAs, each with one of the first six B chunks behind it
-            static_for<0, 6>([&](auto kc) {
-              constexpr int k = decltype(kc)::value;
-              __builtin_amdgcn_sched_barrier(0);
-              t_mfma(k);
-              b_chunk(k);
-            });
-          }
-        };
-        u32x4 bv[2][3];
-        read_frag(r & 1, 0, 0, bv[0]);
-        if constexpr (!FILL) static_for<0, 48>(slot);
-        // ---- 2 k-steps x 4 column tiles x the six cross products; B fragments one tile-step ahead
-        static_for<0, 8>([&](auto nc) {
-          constexpr int n = decltype(nc)::value, ks = n >> 2, b = n & 3;
-          if constexpr (n + 1 < 8) read_frag(r & 1, (n + 1) >> 2, (n + 1) & 3, bv[(n + 1) & 1]);
-          __builtin_amdgcn_sched_barrier(0);
-          constexpr int AT[6] = {2, 0, 1, 1, 0, 0}, BT[6] = {0, 2, 1, 0, 1, 0};  // the six cross products, smallest first
-          static_for<0, 6>([&](auto kc) {
-            constexpr int k6 = decltype(kc)::value;
-            acc2[b] = mfma_bf16(At[AT[k6]][ks], bv[n & 1][BT[k6]], acc2[b]);
-            if constexpr (FILL) slot(std::integral_constant<int, 6 * n + k6>{});
-            __builtin_amdgcn_sched_barrier(0);
-          });
-        });
-        PHASE(6);
-        // the next round's B terms into the buffer the PREVIOUS round read (every wave has passed this round's barrier, i.e.
-        // left the previous round); its A operands become current
-        b_store((r + 1) & 1);
-#pragma unroll
-        for (int t = 0; t < 3; ++t) {
-          At[t][0] = AtN[t][0];
-          At[t][1] = AtN[t][1];
-        }
-        PHASE(7);
-      }
-    });
-  }
-
-  // ---- this workgroup's partial row of dW' | db' straight from the accumulators (disjoint tiles), the unused rows cleared
-  {
-    constexpr long ROW2 = (long)H * H + H;
-    float *mypart = dw2_part + (long)blockIdx.x * ROW2;
-#pragma unroll
-    for (int b = 0; b < 4; ++b)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int o = 32 * wave + (r & 3) + 8 * (r >> 2) + 4 * h;
-        mypart[(long)o * H + 32 * b + i] = acc2[b][r];
-      }
-    const float dbt = wave_sum32(db2);
-    if (h == 0) mypart[(long)H * H + 32 * wave + i] = dbt;
-    for (int row = blockIdx.x + gridDim.x; row < n_part_rows; row += gridDim.x) {
-      float *z = dw2_part + (long)row * ROW2;
-      for (int e = threadIdx.x; e < ROW2; e += WG_THREADS) z[e] = 0.f;
-    }
-  }
-  if constexpr (KT > 0) {
-    f32x16 a1x[4][1];
-#pragma unroll
-    for (int a = 0; a < 4; ++a) a1x[a][0] = acc1[a];
-    finish_partials<4, 1>(a1x, dbs, reinterpret_cast<float *>(img), dw1_part, n_part_rows);
-  }
-  PHASE(11);
-  PHASE_END(3);
-}
-
-// k_bwd_dx_dw8 (HARL_BWD_SPLIT_WAVES = 1, the default): k_bwd_dx_dw with the two parts on waves of their own -- eight waves,
-// two per SIMD, the same 144 KiB of LDS.  Waves 0..3 are the owners (the O part of slab base + w, nothing else), waves 4..7
-// the gradient waves (the D part, row tile w - 4 of dW').  The D part never reads what the O part computes and the two use
-// disjoint LDS (the weight image / the staging buffers), so each SIMD gets a second wave to issue while the other stalls on a
-// load, a barrier or the LayerNorm chain -- what the single wave per SIMD of k_bwd_dx_dw did in 44 % of its phase table.
-// Every wave has half the registers (<= 256: occupancy 2): the owner streams its dz by k-step and requests the LayerNorm /
-// x0n operands late, the gradient waves request the next pieces after the packing instead of beside it.  The slab-to-wave
-// assignment and every MFMA / reduction order are k_bwd_dx_dw's: the same bits (tests/test_gpu_bwd_split_waves.py).
-// s_barrier is workgroup-wide: an owner meets the barrier of each of the four rounds of its super-round once (obar), spread
-// over its slab so that owner segment k runs beside round k; the gradient waves run the rounds of the owners' super-round, so
-// their second read of dz / x_hat_prev follows the owners' first by a few microseconds.  HARL_BWD_SPLIT_WAVES=0 (A/B builds)
-// launches k_bwd_dx_dw.
-#ifndef HARL_BWD_SPLIT_WAVES
-#define HARL_BWD_SPLIT_WAVES 1
-#endif
-template <int KT, bool FILL>
-__global__ __launch_bounds__(2 * WG_THREADS, 1) void k_bwd_dx_dw8(
-    const float *__restrict__ dz, const float *__restrict__ xprev, const uint32_t *__restrict__ mask_prev,
-    const float *__restrict__ rstd_prev, const float *__restrict__ Wp, float *__restrict__ dz_prev, long n_slabs,
-    const float *__restrict__ x0n, float *__restrict__ dw1_part, float *__restrict__ dw2_part, int n_part_rows) {
-  constexpr int H = 128, MT = 4, NJ = 8, NR = 64, KPF = 32, NTH = 2 * WG_THREADS;
-  extern __shared__ __attribute__((aligned(16))) float lds[];
-  PHASE_BEGIN();
-  u32x4 *img = reinterpret_cast<u32x4 *>(lds);
-  unsigned char *Bb = reinterpret_cast<unsigned char *>(img + 3 * MT * NJ * 64);  // [2][3 terms][BDW_IMG]: x_hat_prev^T staging
-  stage_split_matrix<H, H, true, NTH>(img, Wp);
-  __syncthreads();
-  const int lane = threadIdx.x & 63, wave_ = wave_id();
-  const int wave = wave_ & 3;  // owner of slab base + wave / gradient wave of row tile `wave` of dW'
-  const bool owner = wave_ < WAVES_PER_WG;
-  const int i = lane & 31, h = lane >> 5;
-  const u32x4 *wl = img + lane;
-  const long sr_stride = (long)gridDim.x * WAVES_PER_WG;
-  const long base0 = (long)blockIdx.x * WAVES_PER_WG;
-  const Ident ident = make_ident(lane);
-
-  // ---- persistent accumulators
-  f32x16 acc2[4];                 // dW' tiles (row tile = wave, column tiles 0..3)
-  f32x16 acc1[KT > 0 ? 4 : 1];    // dW_1' tiles (KT = 1)
-  float dbs[KT > 0 ? 4 : 1];      // db_1' (per-lane sums over the lane's samples)
-  float db2 = 0.f;                // db' of feature 32 wave + (lane & 31): this lane half's 16 samples of every slab
-  // (each role clears its accumulators in its own branch, and the other role's after its loop: nothing of the other role is
-  // live across a role's loop)
-  auto zero_acc2 = [&]() {
-#pragma unroll
-    for (int b = 0; b < 4; ++b)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc2[b][r] = 0.f;
-  };
-  auto zero_acc1 = [&]() {
-#pragma unroll
-    for (int a = 0; a < (KT > 0 ? 4 : 1); ++a) {
-      dbs[a] = 0.f;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc1[a][r] = 0.f;
-    }
-  };
-
-  // ---- D-part state.  prA: the four float4 pieces 4 wave + u of a slab's dz = registers 16 wave .. 16 wave + 15 of the
-  // accumulator layout = the 32-feature block `wave`; prB: pieces 4 wave + u of x_hat_prev (this wave's quarter of the B operand)
-  f32x4 prA[4], prB[4];
-  u32x2_t spB[4][3];          // split terms of prB: one ds_write_b64 each
-  u32x4 ya[3][2];             // split terms of prA by k-step (split_transpose_block's y1 / y2 / y3)
-  f32x16 tc[3];               // the three transposed terms (lane = feature, 16 samples)
-  u32x4 At[3][2], AtN[3][2];  // A operands [term][k-step] of this round / of the next one
-  float rr0 = 0.f, rr1 = 0.f; // remainders between the two stages of a pair's split
-  auto d_load = [&](long ds) {
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      prA[u] = (reinterpret_cast<const f32x4 *>(dz + ds * (long)(H * SLAB)) + lane)[(4 * wave + u) * WAVE];
-      prB[u] = (reinterpret_cast<const f32x4 *>(xprev + ds * (long)(H * SLAB)) + lane)[(4 * wave + u) * WAVE];
-    }
-  };
-  // Preparing a round that will not be executed (past the last slab) is harmless -- its operands are never multiplied -- except
-  // for the bias sums of its A block: `vnext` (1 or 0) multiplies them.  The loads of such a round are clamped to a valid slab.
-  float vnext = 1.f;
-  auto d_load_next = [&](long ds, long fallback) { d_load(ds < n_slabs ? ds : fallback); };
-  // A chunk k (0..15): pair p = k >> 1 = registers 2p, 2p + 1 of the block -> word p & 3 of k-step p >> 2; stage k & 1
-  auto a_chunk = [&](int k) {
-    const int pi = k >> 1, j = pi >> 2, c = pi & 3, u = pi >> 1, e = 2 * (pi & 1);
-    if ((k & 1) == 0) {
-      unsigned p1;
-      split_stage1(prA[u][e], prA[u][e + 1], p1, rr0, rr1);
-      ya[0][j][c] = p1;
-    } else {
-      unsigned p2, p3;
-      split_stage2(rr0, rr1, p2, p3);
-      ya[1][j][c] = p2;
-      ya[2][j][c] = p3;
-    }
-  };
-  // B chunk k (0..15): piece k >> 2, pair (k >> 1) & 1, stage k & 1
-  auto b_chunk = [&](int k) {
-    const int u = k >> 2, c2 = (k >> 1) & 1;
-    if ((k & 1) == 0) {
-      unsigned p1;
-      split_stage1(prB[u][2 * c2], prB[u][2 * c2 + 1], p1, rr0, rr1);
-      spB[u][0][c2] = p1;
-    } else {
-      unsigned p2, p3;
-      split_stage2(rr0, rr1, p2, p3);
-      spB[u][1][c2] = p2;
-      spB[u][2][c2] = p3;
-    }
-  };
-  // transposing MFMA k (0..5) of the A block: term k % 3, k-step k / 3 (mfma_transpose.h, transpose_block)
-  auto t_mfma = [&](int k) {
-    const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    const int t = k % 3;
-    if (k < 3) tc[t] = mfma_bf16(ya[t][0], ident.j0, zero);
-    else tc[t] = mfma_bf16(ya[t][1], ident.j1, tc[t]);
-  };
-  // pack chunk k (0..5): k < 3: term k -> the two k-step operands; k >= 3: its row sums into db'
-  auto p_chunk = [&](int k) {
-    if (k < 3) {
-      pack_transposed(tc[k], AtN[k][0], AtN[k][1]);
-    } else {
-      f32x2 a = {0.f, 0.f};
-#pragma unroll
-      for (int r = 0; r < 8; ++r) a += f32x2{tc[k - 3][2 * r], tc[k - 3][2 * r + 1]};
-      db2 += vnext * (a[0] + a[1]);
-    }
-  };
-  auto b_store = [&](int buf) {
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const int q = 4 * wave + u;
-      unsigned char *d = Bb + buf * BDW_BUF + (i >> 2) * BDW_SQ + (2 * (q >> 2) + ((q & 3) >> 1)) * 128 + (i & 3) * 32 +
-                         (8 * (q & 1) + 4 * h) * 2;
-#pragma unroll
-      for (int term = 0; term < 3; ++term) *reinterpret_cast<u32x2_t *>(d + term * BDW_IMG) = spB[u][term];
-    }
-  };
-  // B fragment of column tile `tile`, k-step ks: the eight samples sigma(r, h) = (r & 3) + 8 (r >> 2) + 4 h + 16 ks, r = 0..7 --
-  // the order the matrix-pipe transposition leaves the A operand in (mfma_transpose.h): sample quads 4 ks + h and 4 ks + 2 + h
-  const int p16 = lane & 15, g1b = (lane >> 4) & 1;
-  const int frag_lane = g1b * 128 + (p16 >> 2) * 32 + (p16 & 3) * 8;
-  auto read_frag = [&](int buf, int ks, int tile, u32x4 (&f)[3]) {
-#pragma unroll
-    for (int term = 0; term < 3; ++term) {
-      const unsigned char *fp = Bb + buf * BDW_BUF + term * BDW_IMG + (4 * ks + h) * BDW_SQ + 2 * tile * 128 + frag_lane;
-      const u32x2_t lo = tr_read(fp), hi = tr_read(fp + 2 * BDW_SQ);
-      f[term] = u32x4{lo[0], lo[1], hi[0], hi[1]};
-    }
-  };
-
-  // ---- owner state: the slab's raw dz (streamed by k-step) and its split into the B operands of the GEMM
-  float raw[NR];
-  u32x4 g1[NJ], g2[NJ], g3[NJ];
-  // O chunk k (0..63) of the slab's split: pair k>>1 (registers 2p, 2p+1 -> word p&3 of k-step p>>2), stage k&1
-  auto o_chunk = [&](int k) {
-    const int pi = k >> 1, j = pi >> 2, c = pi & 3;
-    if ((k & 1) == 0) {
-      unsigned p1;
-      split_stage1(raw[2 * pi], raw[2 * pi + 1], p1, rr0, rr1);
-      g1[j][c] = p1;
-    } else {
-      unsigned p2, p3;
-      split_stage2(rr0, rr1, p2, p3);
-      g2[j][c] = p2;
-      g3[j][c] = p3;
-    }
-  };
-  // ---- the first round of the first super-round is prepared in the open
-  if (!owner && base0 < n_slabs) {
-    d_load(base0);
-#pragma unroll
-    for (int k = 0; k < 16; ++k) a_chunk(k);
-#pragma unroll
-    for (int k = 0; k < 6; ++k) t_mfma(k);
-#pragma unroll
-    for (int k = 0; k < 16; ++k) b_chunk(k);
-#pragma unroll
-    for (int k = 0; k < 6; ++k) p_chunk(k);
-#pragma unroll
-    for (int t = 0; t < 3; ++t) {
-      At[t][0] = AtN[t][0];
-      At[t][1] = AtN[t][1];
-    }
-    b_store(0);
-  }
-  PHASE(10);
-
-  auto o_part = [&](long base) {
-    const long slab = base + wave;
-    const bool own = slab < n_slabs;
-    // owner barrier k: meets the barrier of weight-gradient round k of this super-round (workgroup-uniform condition:
-    // the rounds run for the slabs that exist).  Placement, by k-step of the dX GEMM (OB1 / OB2: after k-step OBk - 1; NJ: after
-    // the GEMM; NJ + 1: after the LayerNorm backward) -- four owner segments of about one round each.
-    constexpr int OB1 = KT > 0 ? 4 : 3, OB2 = KT > 0 ? NJ : 6, OB3 = KT > 0 ? NJ + 1 : NJ;
-    auto obar = [&](int k) {
-      if (base + k < n_slabs) __builtin_amdgcn_s_barrier();
-    };
-    // =========================== O part: this wave's own slab ===========================
-    if (own) {
-      // dz streamed by k-step (pieces 2j, 2j + 1 of atl_load's layout = raw[8j .. 8j + 7]), RAW_LEAD k-steps ahead of
-      // the split -- a third of the registers a whole slab held; no prefetch across the slabs: the gradient wave on this SIMD
-      // issues while this one waits
-      constexpr int RAW_LEAD = 3;
-      auto raw_ks = [&](int j) {
-        const f32x4 *p = reinterpret_cast<const f32x4 *>(dz + slab * (long)(H * SLAB)) + lane;
-#pragma unroll
-        for (int c = 0; c < 2; ++c) {
-          const f32x4 v = p[(2 * j + c) * WAVE];
-#pragma unroll
-          for (int e = 0; e < 4; ++e) raw[8 * j + 4 * c + e] = v[e];
-        }
-      };
-#pragma unroll
-      for (int j = 0; j < RAW_LEAD; ++j) raw_ks(j);
-      obar(0);
-#pragma unroll
-      for (int k = 0; k < 8; ++k) o_chunk(k);  // k-step 0 (the other seven ride inside the GEMM)
-      float xh[NR];
-      float rstd;
-      uint32_t mbits[2];
-      f32x4 x0r[KT > 0 ? KPF / 8 : 1];
-      auto x0_operands = [&]() {
-        if constexpr (KT > 0) {
-          const f32x4 *bp = reinterpret_cast<const f32x4 *>(x0n + slab * (long)(KPF * SLAB)) + lane;
-#pragma unroll
-          for (int q = 0; q < KPF / 8; ++q) x0r[q] = bp[q * WAVE];
-        }
-      };
-      auto ln_operands = [&]() {
-        atl_load<H>(xprev, slab, lane, xh);
-        rstd = rstd_prev[slab * SLAB + i];
-#pragma unroll
-        for (int w = 0; w < 2; ++w) mbits[w] = mask_prev[(slab * 2 + w) * WAVE + lane];
-      };
-      // the LayerNorm operands are requested at the end of the GEMM, x0n after the LayerNorm backward: across the GEMM, acc,
-      // dW_1', the split terms and the weight fragments hold the registers (the four-wave kernel issued both before it; one
-      // k-step earlier, or x0n with the others, spills)
-      constexpr int LN_STEP = NJ;
-      f32x16 acc[MT];
-#pragma unroll
-      for (int t = 0; t < MT; ++t)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
-      PHASE(0);
-      // the split of k-step j + 1 of the slab's dz (raw) behind the 24 product MFMAs of k-step j, one chunk behind every third
-      // MFMA (as the four-wave kernel), the request of k-step j + RAW_LEAD's dz at its start, the barriers at k-step ends
-      split_gemm_fill<MT, NJ>(wl, g1, g2, g3, acc, [&](int s_, int k6) {
-        const int j1 = s_ / MT + 1, q = (s_ % MT) * 6 + k6;  // q = 0..23: the MFMA's position inside k-step j
-        if (j1 < NJ && q % 3 == 0) o_chunk(8 * j1 + q / 3);
-        if (s_ % MT == 0 && k6 == 0 && j1 - 1 + RAW_LEAD < NJ) raw_ks(j1 - 1 + RAW_LEAD);
-        if (s_ % MT == MT - 1 && k6 == 5) {  // end of k-step j1 - 1
-          if (j1 == LN_STEP) ln_operands();
-          if (j1 == OB1) obar(1);
-          if (j1 == OB2) obar(2);
-          if (j1 == OB3) obar(3);
-        }
-      });
-      PHASE(1);
-      float dx[NR];
-#pragma unroll
-      for (int R = 0; R < NR; ++R) dx[R] = acc[R >> 4][R & 15];
-      float out[NR];
-      ln_bwd_relu_mbits<H>(dx, xh, mbits, rstd, out);
-      if (dz_prev) atl_store<H>(dz_prev, slab, lane, out);
-      x0_operands();
-      if constexpr (OB3 == NJ + 1) obar(3);
-      PHASE(2);
-      if constexpr (KT > 0) {
-        float xr0[KPF / 2];
-#pragma unroll
-        for (int q = 0; q < KPF / 8; ++q) {
-          xr0[4 * q + 0] = x0r[q][0];
-          xr0[4 * q + 1] = x0r[q][1];
-          xr0[4 * q + 2] = x0r[q][2];
-          xr0[4 * q + 3] = x0r[q][3];
-        }
-        u32x4 a1[KPF / 16], a2[KPF / 16], a3[KPF / 16];
-        split_acts<KPF / 2>(xr0, a1, a2, a3);
-        u32x4 Bt[3][2];
-        transpose_block<false>(a1[0], a1[1], a2[0], a2[1], a3[0], a3[1], ident, Bt);
-#pragma unroll
-        for (int a = 0; a < 4; ++a) {
-          u32x4 A1[3][2];
-          dbs[a] += split_transpose_block<true>(&out[16 * a], ident, A1);
-          dw_tile(acc1[a], A1, Bt);
-        }
-        PHASE(3);
-      }
-    }
-    else {  // no slab for this owner in the last super-round; it still meets the rounds' barriers
-#pragma unroll
-      for (int k = 0; k < 4; ++k) obar(k);
-    }
-  };
-  auto d_part = [&](long base) {
-    // =========================== D part: the four slabs of this super-round ===========================
-    // this wave's pieces of round 1 (round 0's operands were prepared by the previous super-round's last round / the prologue)
-    d_load_next(base + 1, base);
-    PHASE(4);
-    static_for<0, 4>([&](auto rc) {
-      constexpr int r = decltype(rc)::value;
-      if (base + r < n_slabs) {  // workgroup-uniform
-        __syncthreads();  // every wave's B terms of this round are in buffer r & 1; buffer (r + 1) & 1 is free
-        PHASE(5);
-        // the round being prepared (r + 1, or round 0 of the next super-round) and the one whose pieces are requested (r + 2; none
-        // from round 3: the next super-round fetches its round 1 itself)
-        const long ds1 = r < 3 ? base + r + 1 : base + sr_stride;
-        const long ds2 = r < 2 ? base + r + 2 : base + sr_stride;
-        vnext = uniform_f(ds1 < n_slabs ? 1.f : 0.f);
-        // TSLOT: the product MFMA behind which the six transposing MFMAs are issued
-        constexpr int TSLOT = r == 0 ? 31 : 15;
-        auto slot = [&](auto sc) {  // filler work behind product MFMA s (0..47)
-          constexpr int s_ = decltype(sc)::value;
-          if constexpr (r == 0) {  // the pieces of round 1 were requested just above: nothing in the first 16 slots
-            if constexpr (s_ >= 16 && s_ < 32) a_chunk(s_ - 16);
-            else if constexpr (s_ >= 32 && s_ < 42) b_chunk(s_ - 32 + 6);
-            else if constexpr (s_ >= 42) p_chunk(s_ - 42);
-            if constexpr (s_ == 47) d_load_next(ds2, base);  // (four-wave kernel: slot 41 / 25 -- here not beside tc)
-          } else {
-            if constexpr (s_ < 16) a_chunk(s_);
-            else if constexpr (s_ < 26) b_chunk(s_ - 16 + 6);
-            else if constexpr (s_ < 32) p_chunk(s_ - 26);
-            if constexpr (s_ == 31 && r < 3) d_load_next(ds2, base);
-          }
-          if constexpr (s_ == TSLOT) {  // the six transposing MFMAs, each with one of the first six B chunks behind it
-            static_for<0, 6>([&](auto kc) {
-              constexpr int k = decltype(kc)::value;
-              __builtin_amdgcn_sched_barrier(0);
-              t_mfma(k);
-              b_chunk(k);
-            });
-          }
-        };
-        u32x4 bv[2][3];
-        read_frag(r & 1, 0, 0, bv[0]);
-        if constexpr (!FILL) static_for<0, 48>(slot);
-        // ---- 2 k-steps x 4 column tiles x the six cross products; B fragments one tile-step ahead
-        static_for<0, 8>([&](auto nc) {
-          constexpr int n = decltype(nc)::value, ks = n >> 2, b = n & 3;
-          if constexpr (n + 1 < 8) read_frag(r & 1, (n + 1) >> 2, (n + 1) & 3, bv[(n + 1) & 1]);
-          __builtin_amdgcn_sched_barrier(0);
-          constexpr int AT[6] = {2, 0, 1, 1, 0, 0}, BT[6] = {0, 2, 1, 0, 1, 0};  // the six cross products, smallest first
-          static_for<0, 6>([&](auto kc) {
-            constexpr int k6 = decltype(kc)::value;
-            acc2[b] = mfma_bf16(At[AT[k6]][ks], bv[n & 1][BT[k6]], acc2[b]);
-            if constexpr (FILL) slot(std::integral_constant<int, 6 * n + k6>{});
-            __builtin_amdgcn_sched_barrier(0);
-          });
-        });
-        PHASE(6);
-        // the next round's B terms into the buffer the PREVIOUS round read (every wave has passed this round's barrier, i.e.
-        // left the previous round); its A operands become current
-        b_store((r + 1) & 1);
-#pragma unroll
-        for (int t = 0; t < 3; ++t) {
-          At[t][0] = AtN[t][0];
-          At[t][1] = AtN[t][1];
-        }
-        PHASE(7);
-      }
-    });
-  };
-  if (owner) {
-    zero_acc1();
-    for (long base = base0; base < n_slabs; base += sr_stride) o_part(base);
-    zero_acc2();
-  } else {
-    zero_acc2();
-    for (long base = base0; base < n_slabs; base += sr_stride) d_part(base);
-    zero_acc1();
-  }
-
-  // ---- this workgroup's partial row of dW' | db' straight from the accumulators (disjoint tiles), the unused rows cleared
-  {
-    constexpr long ROW2 = (long)H * H + H;
-    float *mypart = dw2_part + (long)blockIdx.x * ROW2;
-    if (!owner) {
-#pragma unroll
-      for (int b = 0; b < 4; ++b)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int o = 32 * wave + (r & 3) + 8 * (r >> 2) + 4 * h;
-          mypart[(long)o * H + 32 * b + i] = acc2[b][r];
-        }
-      const float dbt = wave_sum32(db2);
-      if (h == 0) mypart[(long)H * H + 32 * wave + i] = dbt;
-    }
-    for (int row = blockIdx.x + gridDim.x; row < n_part_rows; row += gridDim.x) {
-      float *z = dw2_part + (long)row * ROW2;
-      for (int e = threadIdx.x; e < ROW2; e += NTH) z[e] = 0.f;
-    }
-  }
-  if constexpr (KT > 0) {  // the owners' accumulators (waves 0..3; the gradient waves' are zero and not read)
-    f32x16 a1x[4][1];
-#pragma unroll
-    for (int a = 0; a < 4; ++a) a1x[a][0] = acc1[a];
-    finish_partials<4, 1, NTH>(a1x, dbs, reinterpret_cast<float *>(img), dw1_part, n_part_rows);
-  }
-  PHASE(11);
-  PHASE_END_BY(4, 0);                     // wave 0: the owner's phases
-  PHASE_END_BY(5, 64 * WAVES_PER_WG);     // wave 4: the gradient waves' phases
-}
+#include "bwd_fused.h"  // the fused hidden-layer backward (k_bwd_dx_dw, k_bwd_dx_dw8): this translation unit, its own file
 
 HARL_PHASE_ACCESSOR(mlp)
 
