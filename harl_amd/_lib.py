@@ -63,6 +63,8 @@ SIGNATURES = {
     "harl_reduce_partials_multi": [_vp, _vp, _i, _i, _l, _vp, _vp],
     "harl_adam_fold": [_vp, _vp, _vp, _vp, _l, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _i, _f, _i, _i, _vp, _i, _f, _d, _d,
                        _d, _f, _f, _d, _d, _vp, _vp],
+    "harl_adam_fold_dev": [_vp, _vp, _vp, _vp, _l, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _i, _f, _i, _i, _vp, _i, _f, _vp, _i,
+                           _vp, _d, _d, _f, _f, _vp, _vp],
     "harl_pack_scalars_hilo": [_vp, _vp, _vp],
     "harl_reduce_pack_scalars": [_vp, _i, _vp, _vp, _vp],
     "harl_randperm_replay": [_vp, _l, _l, _vp, _vp, _vp],

@@ -1184,14 +1184,28 @@ __device__ __forceinline__ float adam_elem(float g_raw, float pi, float &mi, flo
   return pi - c.lr_over_bc1 * (mi / (sqrtf(vi) / c.bc2_sqrt + c.eps));
 }
 
+// DEV (harl_adam_fold_dev): the step size and sqrt(bias_correction2) do not arrive as launch arguments but come from row
+// step_idx[0] of the device table hyper[n_hyper][3] = {lr, bias_correction1, bias_correction2} -- the same two host expressions
+// of harl_adam_fold, (float)(lr / bc1) and (float)sqrt(bc2), in IEEE double arithmetic -- so that ONE captured launch serves
+// every replay of a hipGraph.  Every workgroup reads the counter on entry; one thread advances it behind the grid barrier.
+template <bool DEV>
 __global__ __launch_bounds__(ADAM_THREADS) void k_adam_fold(
     float *__restrict__ p, float *__restrict__ g, float *__restrict__ m, float *__restrict__ v, long n,
     const float *__restrict__ dwp, const int *__restrict__ tab, int n_layers,
     float *__restrict__ packs, double *__restrict__ scalars, const float *__restrict__ part_scalars, int n_scalar_blocks,
     const float *__restrict__ scalars_hilo, int mode, float const_scale, int logstd_off, int act_dim, double *__restrict__ info, int use_clip, float max_norm,
     float lr_over_bc1, float beta1, float beta2, float omb1, float omb2, float eps, float wd, float bc2_sqrt,
-    unsigned *__restrict__ ws) {
+    unsigned *__restrict__ ws, const double *__restrict__ hyper, int n_hyper, int *step_idx) {
   __shared__ double sh[64];
+  int step_now = 0;
+  if constexpr (DEV) {
+    // (an atomic load: a vector load that is issued here, in front of the barrier, whatever the optimiser makes of the rest)
+    step_now = __hip_atomic_load(step_idx, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const int row = step_now < 0 ? 0 : (step_now < n_hyper ? step_now : n_hyper - 1);  // past the table: its last row
+    const double *h = hyper + 3 * (long)row;
+    lr_over_bc1 = (float)(h[0] / h[1]);
+    bc2_sqrt = (float)sqrt(h[2]);
+  }
   const int tid = threadIdx.x, nt = ADAM_THREADS;
   const int G = gridDim.x, blk = blockIdx.x;
   const long gtid = (long)blk * nt + tid, gnt = (long)G * nt;
@@ -1283,6 +1297,9 @@ __global__ __launch_bounds__(ADAM_THREADS) void k_adam_fold(
   }
   bar_target += (unsigned)G;
   grid_barrier(ws, bar_target);
+  if constexpr (DEV) {  // every workgroup read the counter in front of the barrier
+    if (blk == 0 && tid == 0) step_idx[0] = step_now + 1;
+  }
   // ---- phase 2.0: every workgroup: the scalar sums (same fixed order everywhere); workgroup 0 publishes them
   if (tid < PS_STRIDE) {
     double t = 0;
@@ -1441,11 +1458,29 @@ extern "C" int harl_adam_fold(float *param, float *grad, float *exp_avg, float *
   if (!ws) { set_error("harl_adam_fold: workspace (>= 32 KiB, zero-initialised once) is required"); return -2; }
   const float step_size = (float)(lr / bias_correction1);
   const float bc2_sqrt = (float)sqrt(bias_correction2);
-  hipLaunchKernelGGL(k_adam_fold, dim3(ADAM_WGS), dim3(ADAM_THREADS), 0, (hipStream_t)stream, param, grad, exp_avg,
+  hipLaunchKernelGGL(k_adam_fold<false>, dim3(ADAM_WGS), dim3(ADAM_THREADS), 0, (hipStream_t)stream, param, grad, exp_avg,
                      exp_avg_sq, n, dwp, table, n_layers, packs, scalars, part_scalars, n_scalar_blocks,
                      scalars_hilo, mode, const_scale, logstd_off, act_dim, info, use_clip, max_norm, step_size, (float)beta1,
-                     (float)beta2, (float)(1.0 - beta1), (float)(1.0 - beta2), eps, weight_decay, bc2_sqrt, (unsigned *)ws);
+                     (float)beta2, (float)(1.0 - beta1), (float)(1.0 - beta2), eps, weight_decay, bc2_sqrt, (unsigned *)ws,
+                     (const double *)nullptr, 0, (int *)nullptr);
   return check_launch("harl_adam_fold");
+}
+
+// harl_adam_fold with {lr, bias_correction1, bias_correction2} taken from row step_idx[0] of a device table (see k_adam_fold)
+extern "C" int harl_adam_fold_dev(float *param, float *grad, float *exp_avg, float *exp_avg_sq, long n, const float *dwp,
+                                  const int *table, int n_layers, float *packs, double *scalars,
+                                  const float *part_scalars, int n_scalar_blocks, const float *scalars_hilo, int mode,
+                                  float const_scale, int logstd_off, int act_dim, double *info, int use_clip, float max_norm,
+                                  const double *hyper, int n_hyper_rows, int *step_idx, double beta1, double beta2, float eps,
+                                  float weight_decay, void *ws, void *stream) {
+  if (!ws) { set_error("harl_adam_fold_dev: workspace (>= 32 KiB, zero-initialised once) is required"); return -2; }
+  if (!hyper || !step_idx || n_hyper_rows < 1) { set_error("harl_adam_fold_dev: hyper table (>= 1 row) and step counter are required"); return -2; }
+  hipLaunchKernelGGL(k_adam_fold<true>, dim3(ADAM_WGS), dim3(ADAM_THREADS), 0, (hipStream_t)stream, param, grad, exp_avg,
+                     exp_avg_sq, n, dwp, table, n_layers, packs, scalars, part_scalars, n_scalar_blocks,
+                     scalars_hilo, mode, const_scale, logstd_off, act_dim, info, use_clip, max_norm, 0.f, (float)beta1,
+                     (float)beta2, (float)(1.0 - beta1), (float)(1.0 - beta2), eps, weight_decay, 0.f, (unsigned *)ws, hyper,
+                     n_hyper_rows, step_idx);
+  return check_launch("harl_adam_fold_dev");
 }
 
 // =============================================================================================

@@ -14,7 +14,7 @@ from typing import Optional
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, graphs
 from ._lib import PS_STRIDE, call, ptr, stream
 from .buffers import OnPolicyActorBuffer, consume_randperm, minibatch_indices, rng_sync
 from .dist import Comm, local_minibatch_rows
@@ -45,6 +45,29 @@ class OnPolicyBase:
         self.comm = Comm()
         self.shard = None  # (n_global, lo, hi) when n_rollout_threads is sharded across ranks
         self._old_logp: Optional[torch.Tensor] = None
+        self._graph = graphs.GraphedStep("the actor")  # HARL_GRAPH=1: captured optimiser steps (HAPPO / HAA2C / MAPPO)
+        self._graph_bufs: dict = {}   # persistent copies of what arrives as a fresh tensor per train()
+        self._graph_gen = None
+
+    def graph_stats(self) -> dict:
+        """dict(captures, replays, eager_steps) of this actor's optimiser steps under HARL_GRAPH=1 (all zero without it)."""
+        return self._graph.stats()
+
+    def _graph_config_ok(self) -> bool:
+        """HARL_GRAPH=1 and a configuration whose optimiser steps may be replayed from a hipGraph: feed-forward, one action
+        head (Gaussian / Categorical), no data parallelism.  Everything else stays eager, exactly as without the variable."""
+        return (graphs.enabled() and not (self.use_recurrent_policy or self.use_naive_recurrent_policy)
+                and not self.actor.recurrent and not self.actor.md and not self.comm.enabled and self.shard is None)
+
+    def _graph_stage(self, name: str, t: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
+        """Copy ``t`` into this actor's persistent buffer ``name`` (a captured step holds ADDRESSES)."""
+        if t is None:
+            return None
+        b = self._graph_bufs.get(name)
+        if b is None or b.shape != t.shape or b.dtype != t.dtype or b.device != t.device:
+            b = self._graph_bufs[name] = torch.empty_like(t, memory_format=torch.contiguous_format)
+        b.copy_(t)
+        return b
 
     def lr_decay(self, episode, episodes):  # utils/models_tools.py:77-87
         lr = self.lr - (self.lr * ((episode - 1) / float(episodes)))
@@ -352,10 +375,44 @@ class HAPPO(OnPolicyBase):
             self._grad_tap(net.flat_grad * float(1.0 / sc[1].item()), sc.clone())
 
     def _update_core(self, obs, idx, m, actions, avail, old_logp, adv, adv_moments, factor, active, seq=None,
-                     logp_out=None):
-        nblk = self._forward_backward(obs, idx, m, actions, avail, old_logp, adv, adv_moments, factor, active, seq=seq,
-                                      logp_out=logp_out)
-        self._optimizer_step(nblk)
+                     logp_out=None, _graph=False):
+        def step():
+            nblk = self._forward_backward(obs, idx, m, actions, avail, old_logp, adv, adv_moments, factor, active, seq=seq,
+                                          logp_out=logp_out)
+            self._optimizer_step(nblk)
+        if not _graph:
+            return step()
+        # HARL_GRAPH=1 (graphs.py): replay this step from a hipGraph.  Eager all the same: the epoch-0 step that also emits the
+        # pre-update log-probs, steps under a test hook (they read back / clone between the launches), instrumented steps.
+        G, net, opt = self._graph, self.actor, self.actor_optimizer
+        if (seq is not None or self._trace is not None or self._grad_tap is not None
+                or self._state_tap is not None or not graphs.launches_capturable(self.device) or opt.hyper_rows_left() < 1):
+            return G.eager(step)
+        warm = (m, idx is None, avail is None, adv_moments is None, factor is None, active is None) + self._graph_consts()
+        if logp_out is not None:
+            # never captured (the output exists in the first epoch only) -- but it is the launch sequence of the later epochs,
+            # kernel for kernel and size for size (log-probs are one more pointer to the same loss launch), so it has raised
+            # every LDS limit they need: it counts as their eager first run
+            G.eager(step)
+            G.warm.add(warm)
+            return
+        self._await_factor()          # (cross-stream waits stay in front of the region)
+        net.prepare_x0n(obs, idx, m)  # ... and so does the launch that depends on a host-side cache
+        if self._graph_gen != net._ws_gen:
+            G.drop()
+            self._graph_gen = net._ws_gen
+        p = lambda t: 0 if t is None else t.data_ptr()  # noqa: E731
+        key = warm + (p(obs), p(idx), p(actions), p(avail), p(old_logp), p(adv), p(adv_moments), p(factor), p(active),
+                      p(self._info), p(net.flat_param), p(net.pack_arena), p(opt.exp_avg), p(opt._hyper_dev), opt._hyper_rows)
+        G.run(warm, key, step, opt)
+
+    def _graph_consts(self) -> tuple:
+        """Host scalars and routing switches that are baked into the launches of an optimiser step."""
+        g = self.actor_optimizer.param_groups[0]
+        e = os.environ.get
+        return (float(self.clip_param), float(self.entropy_coef), self.action_aggregation, self._surrogate_mode,
+                bool(self.use_max_grad_norm), float(self.max_grad_norm), tuple(g["betas"]), float(g["eps"]),
+                float(g["weight_decay"]), e("HARL_FUSED_UPDATE"), e("HARL_BWD_FUSED"), e("HARL_BWD_K64"), e("HARL_TRUNK_FUSED"))
 
     def update(self, sample):
         """API-compatible single update on an already-gathered minibatch (tuple order of happo.py:37-48).
@@ -452,6 +509,33 @@ class HAPPO(OnPolicyBase):
         old_logp = buf.flat("action_log_probs")
         factor = None if buf.factor is None else buf.factor.reshape(B)  # None: MAPPO (no sequential-update factor)
         n_global = self.shard[0] * T if self.shard else B
+        graph = False
+        if self._graph_config_ok():
+            # HARL_GRAPH=1: the Adam scalars of the coming steps go to the device once (FusedAdam.begin_steps); what arrives as a
+            # fresh tensor per call -- advantages, their moments, the factor -- moves into persistent buffers, because a
+            # captured step holds addresses
+            self.actor_optimizer.begin_steps(self.ppo_epoch * self.actor_num_mini_batch)
+            graph = graphs.launches_capturable(dev)
+        if graph:
+            self._await_factor()
+            adv, moments, factor = (self._graph_stage("adv", adv), self._graph_stage("moments", moments),
+                                    self._graph_stage("factor", factor))
+        try:
+            self._train_epochs(buf, obs, actions, avail, old_logp, adv, moments, factor, active, B, n_global, _old_logp_out, graph)
+        finally:
+            self.actor_optimizer.end_steps()
+        n_upd = self.ppo_epoch * self.actor_num_mini_batch
+        if _defer:
+            return self._info / n_upd
+        rng_sync()
+        vals = (self._info / n_upd).cpu().tolist()  # the single read-back of this agent's update
+        for k, v in zip(self._INFO_KEYS, vals):
+            train_info[k] = v
+        return train_info
+
+    def _train_epochs(self, buf, obs, actions, avail, old_logp, adv, moments, factor, active, B, n_global, _old_logp_out,
+                      graph: bool) -> None:
+        dev = self.device
         for epoch in range(self.ppo_epoch):
             if self.use_recurrent_policy or self.use_naive_recurrent_policy:
                 for seq in buf.recurrent_batches(self.actor_num_mini_batch, self.data_chunk_length,
@@ -468,7 +552,7 @@ class HAPPO(OnPolicyBase):
                 consume_randperm(n_global)
                 self._update_core(obs, None, B, actions, avail, old_logp, adv, moments, factor,
                                   active if self.use_policy_active_masks else None,
-                                  logp_out=_old_logp_out if epoch == 0 else None)
+                                  logp_out=_old_logp_out if epoch == 0 else None, _graph=graph)
                 continue
             sampler = minibatch_indices(n_global, self.actor_num_mini_batch, dev)  # CPU RNG draw, bit-exact with the reference
             for ind in sampler:
@@ -477,16 +561,9 @@ class HAPPO(OnPolicyBase):
                     if ind.numel() == 0:
                         self._optimizer_step(0)
                         continue
-                self._update_core(obs, ind.to(dev), ind.numel(), actions, avail, old_logp, adv, moments, factor,
-                                  active if self.use_policy_active_masks else None)
-        n_upd = self.ppo_epoch * self.actor_num_mini_batch
-        if _defer:
-            return self._info / n_upd
-        rng_sync()
-        vals = (self._info / n_upd).cpu().tolist()  # the single read-back of this agent's update
-        for k, v in zip(self._INFO_KEYS, vals):
-            train_info[k] = v
-        return train_info
+                # (graph mode: every minibatch's rows go through ONE persistent index buffer, minibatches are of equal size)
+                self._update_core(obs, self._graph_stage("idx", ind) if graph else ind.to(dev), ind.numel(), actions, avail,
+                                  old_logp, adv, moments, factor, active if self.use_policy_active_masks else None, _graph=graph)
 
 
 class HAA2C(HAPPO):

@@ -13,7 +13,7 @@ from typing import List
 
 import torch
 
-from . import _lib
+from . import _lib, graphs
 from ._lib import call, ptr, stream
 from .buffers import OnPolicyActorBuffer, consume_randperm, minibatch_indices, rng_sync
 from .dist import local_minibatch_rows
@@ -57,6 +57,28 @@ class MAPPO(HAPPO):
         n_global = self.shard[0] * T if self.shard else B
         k = self.actor_num_mini_batch
         s = stream()
+        graph = False
+        if self._graph_config_ok():  # HARL_GRAPH=1 (graphs.py, HAPPO.train): one graph per optimiser step = all agents' segments
+            self.actor_optimizer.begin_steps(self.ppo_epoch * k)
+            graph = graphs.launches_capturable(dev)
+        if graph:  # persistent copies of what is a fresh tensor per call
+            acc = self._graph_stage("acc", acc)
+            moments = self._graph_stage("moments", moments)
+            adv_a = ([self._graph_stage("adv", adv_a[0])] * A if state_type == "EP"
+                     else [self._graph_stage(f"adv{a}", adv_a[a]) for a in range(A)])
+        try:
+            self._share_param_epochs(actor_buffer, adv_a, moments, acc, A, B, n_global, k, s, graph)
+        finally:
+            self.actor_optimizer.end_steps()
+        n_upd = self.ppo_epoch * k
+        if _defer:
+            return self._info / n_upd
+        rng_sync()
+        vals = (self._info / n_upd).cpu().tolist()
+        return dict(zip(self._INFO_KEYS, vals))
+
+    def _share_param_epochs(self, actor_buffer, adv_a, moments, acc, A, B, n_global, k, s, graph: bool) -> None:
+        dev, net = self.device, self.actor
         for _ in range(self.ppo_epoch):
             # every agent's generator draws its own permutation, in agent order, when the first minibatch is requested
             samplers = []
@@ -67,15 +89,17 @@ class MAPPO(HAPPO):
                 else:
                     samplers.append(minibatch_indices(n_global, k, dev))
             for b in range(k):
-                acc.zero_()
-                net._ensure_ws(B)
-                net.scalars.zero_()
                 segs = []
                 for a in range(A):
                     ind = samplers[a][b]
                     if ind is not None and self.shard:
                         ind = local_minibatch_rows(ind, self.shard[0], self.shard[1], self.shard[2])
-                    segs.append(None if ind is None else ind.to(dev))
+                    segs.append(None if ind is None else self._graph_stage(f"idx{a}", ind) if graph else ind.to(dev))
+                if graph and self._share_param_step_graphed(actor_buffer, segs, adv_a, moments, acc, A, B):
+                    continue
+                acc.zero_()
+                net._ensure_ws(B)
+                net.scalars.zero_()
                 if net.md and self.use_policy_active_masks:
                     # MultiDiscrete: sum(active) / rows of the CONCATENATED minibatch (happo._md_ent_scale; mappo.py:185-234)
                     st = torch.zeros(2, dtype=torch.float32, device=dev)
@@ -99,12 +123,46 @@ class MAPPO(HAPPO):
                 self._md_ent_override = None
                 net.dwp.copy_(acc)
                 self._optimizer_step(None)
-        n_upd = self.ppo_epoch * k
-        if _defer:
-            return self._info / n_upd
-        rng_sync()
-        vals = (self._info / n_upd).cpu().tolist()
-        return dict(zip(self._INFO_KEYS, vals))
+
+    def _share_param_step_graphed(self, actor_buffer, segs, adv_a, moments, acc, A, B) -> bool:
+        """HARL_GRAPH=1: one optimiser step of the shared actor -- every agent's segment, the accumulation, the optimiser launch --
+        replayed from ONE hipGraph.  The normalised-input image is rebuilt for every segment inside the step, whatever the
+        host-side cache says (consecutive segments read different buffers: it misses anyway), so that the captured sequence
+        is the executed one.  False: not eligible right now, the caller runs the step as always."""
+        G, net, opt = self._graph, self.actor, self.actor_optimizer
+        if (self._trace is not None or self._grad_tap is not None or self._state_tap is not None
+                or not graphs.launches_capturable(self.device) or opt.hyper_rows_left() < 1):
+            G.eager_steps += 1
+            return False
+        use_active = self.use_policy_active_masks
+        bufs = [(b.flat("obs"), b.flat("actions"), None if b.available_actions is None else b.flat("available_actions"),
+                 b.flat("action_log_probs"), b.flat("active_masks").reshape(B) if use_active else None) for b in actor_buffer[:A]]
+
+        def step():
+            acc.zero_()
+            net.scalars.zero_()
+            for a in range(A):
+                obs, actions, avail, old_logp, active = bufs[a]
+                m = B if segs[a] is None else segs[a].numel()
+                nblk = self._forward_backward(obs, segs[a], m, actions, avail, old_logp, adv_a[a], moments, None, active)
+                acc.add_(net.dwp)
+                call("harl_reduce_scalars", ptr(net.part_scalars), nblk, ptr(net.scalars), stream())  # (the stream of the capture, if any)
+            net.dwp.copy_(acc)
+            self._optimizer_step(None)
+        net._ensure_ws(B)
+        if self._graph_gen != net._ws_gen:
+            G.drop()
+            self._graph_gen = net._ws_gen
+        p = lambda t: 0 if t is None else t.data_ptr()  # noqa: E731
+        warm = ("shared", A, tuple(B if g is None else g.numel() for g in segs), moments is None, use_active) + self._graph_consts()
+        key = warm + tuple(p(t) for row in bufs for t in row) + tuple(p(g) for g in segs) + tuple(p(t) for t in adv_a) + (
+            p(moments), p(acc), p(self._info), p(net.flat_param), p(net.pack_arena), p(opt.exp_avg), p(opt._hyper_dev), opt._hyper_rows)
+        net._x0n_force, net._x0n_key = True, None
+        try:
+            G.run(warm, key, step, opt)
+        finally:
+            net._x0n_force, net._x0n_key = False, None
+        return True
 
     def _share_param_train_recurrent(self, actor_buffer, adv, A: int, state_type: str, _moments, _defer: bool):
         """Parameter sharing with GRU policies (mappo.py:185-234).  The reference concatenates the agents' recurrent samples

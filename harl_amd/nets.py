@@ -20,6 +20,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
+from . import graphs as _graphs
 from ._lib import DHEAD_LD, PS_STRIDE, SLAB, call, ptr, stream
 
 SUPPORTED_WIDTHS = (64, 128, 256)
@@ -135,6 +136,7 @@ class _FlatNet(nn.Module):
         self.in_dim = in_dim
         self.wide = 32 < in_dim <= 512  # first layer through the cached x0n image (csrc/wide.hip); <= 32: fused 2-layer kernel
         self._x0n_key = None
+        self._x0n_force = False  # build the image whatever the cache says (graphs.py: several buffers inside ONE captured step)
         self.md = False  # MultiDiscrete heads (StochasticPolicy)
         self._md_sp: List[int] = []
         self._cpu_params: List[Tuple[str, torch.Tensor]] = []
@@ -299,6 +301,7 @@ class _FlatNet(nn.Module):
             dwp_off += elems
         self._table_rows = rows
         self.n_entries = len(rows)
+        self._ws_gen = getattr(self, "_ws_gen", 0) + 1  # (captured optimiser steps hold the arenas' addresses: graphs.py)
         self.pack_arena = torch.zeros(pack_off, dtype=torch.float32, device=dev)
         # the dense folded gradients live at the head of the data-parallel all-reduce message: [dwp | 4 fixed-grid scalar pieces] (dist.py)
         self.dwp_msg = torch.zeros(dwp_off + 4 * PS_STRIDE, dtype=torch.float32, device=dev)
@@ -355,6 +358,7 @@ class _FlatNet(nn.Module):
         if M <= self._max_rows:
             return
         dev = self.device_
+        self._ws_gen = getattr(self, "_ws_gen", 0) + 1  # every workspace below gets a new address
         n_slabs = (M + SLAB - 1) // SLAB
         mp = n_slabs * SLAB
         f32, u32 = torch.float32, torch.int32
@@ -483,10 +487,34 @@ class _FlatNet(nn.Module):
         # both tensors alive, so an equal address cannot belong to a recycled allocation with other rows in it
         key = ((X.data_ptr(), X._version, tuple(X.shape), M) if idx is None
                else (X.data_ptr(), X._version, tuple(X.shape), M, idx.data_ptr(), idx._version, idx.numel()))
-        if key != self._x0n_key:
+        if key != self._x0n_key or self._x0n_force:
+            if _graphs.capturing() and not self._x0n_force:
+                # a launch that depends on this host-side cache must not end up in a graph that is replayed whatever the
+                # cache says: the caller builds the image in front of the captured region (prepare_x0n)
+                raise RuntimeError("the normalised-input image is not up to date inside a captured optimiser step")
             call("harl_mlp_x0n_wide", ptr(X), X.shape[1], ptr(idx), M, self.in_dim, int(self.use_feature_normalization),
                  ptr(self.x0n), ptr(self.mu0), ptr(self.rstd0), s, tag="x0n_wide")
             self._x0n_key, self._x0n_src = key, (X, idx)
+
+    def prepare_x0n(self, X: torch.Tensor, idx: Optional[torch.Tensor], M: int) -> None:
+        """HARL_GRAPH=1, in front of a captured optimiser step (graphs.py): build the normalised-input image NOW if this
+        network's step reads one, so that the step itself finds it cached -- the image launch depends on a host-side cache
+        (first step of an update: miss, later ones: hit) and a replayed graph repeats what was captured.  Same launch, same
+        place in the stream as the eager step's.  Mirrors the routes of fused_args / forward_trunk; a route this gets wrong
+        fails the capture (_x0n_image), it never replays a stale image."""
+        hs = self.hidden_sizes
+        self._ensure_ws(M)
+        two_equal = len(hs) >= 2 and hs[0] == hs[1]
+        if self.act_id or self.panel or self.trunk_fused():
+            self._x0n_image(X, M, stream(), idx)
+        elif two_equal and self.in_dim <= 64 and idx is None:
+            self._x0n_image(X, M, stream())
+        elif two_equal and self.in_dim <= 32:
+            self._x0n_key = None  # harl_mlp_fwd_fused2 writes the gathered minibatch's image into self.x0n
+        elif self.wide:
+            self._x0n_image(X, M, stream(), idx)
+        else:
+            self._x0n_key = None  # harl_mlp_fwd_input may write self.x0n
 
     def invalidate_caches(self) -> None:
         """Drop the cached normalised-input image.  The cache key is (data_ptr, torch version counter, shape, rows): it
@@ -1210,6 +1238,10 @@ class FusedAdam:
         self.exp_avg_sq = torch.zeros_like(net.flat_param)
         self.step_count = 0
         self._ws = torch.zeros(8192, dtype=torch.int32, device=net.flat_param.device)  # grid-barrier words + partials
+        # HARL_GRAPH=1 (begin_steps): {lr, 1 - b1^t, 1 - b2^t} of the upcoming steps behind one counter word, host + device
+        self._hyper_host = self._hyper_dev = self._hyper_ev = None
+        self._hyper_base: Optional[int] = None  # step_count at begin_steps while the device table is armed
+        self._hyper_rows = 0
 
     def zero_grad(self) -> None:  # gradients are overwritten, never accumulated
         return None
@@ -1222,16 +1254,72 @@ class FusedAdam:
         (single-GPU path); ``scalars_hilo``: the all-reduced fixed-grid fp32 pieces behind the gradients in ``net.dwp_msg``
         (data-parallel path); neither = ``net.scalars`` already holds the sums."""
         g = self.param_groups[0]
+        row = -1 if self._hyper_base is None else self.step_count - self._hyper_base
         self.step_count += 1
         b1, b2 = g["betas"]
+        n = self.net
+        if 0 <= row < self._hyper_rows:
+            # armed (begin_steps): lr and the bias corrections of this step are row `row` of the device table, which is where
+            # the device counter stands -- every step since begin_steps went through this launch
+            call("harl_adam_fold_dev", ptr(n.flat_param), ptr(n.flat_grad), ptr(self.exp_avg), ptr(self.exp_avg_sq), n.n_params,
+                 ptr(n.dwp), ptr(n.table), n.n_entries, ptr(n.pack_arena), ptr(n.scalars), ptr(part_scalars),
+                 int(n_scalar_blocks), ptr(scalars_hilo), int(mode), float(const_scale), int(logstd_off), int(act_dim),
+                 ptr(info_out), int(use_clip), float(max_norm), self._hyper_dev.data_ptr() + 8, self._hyper_rows,
+                 self._hyper_dev.data_ptr(), float(b1), float(b2), float(g["eps"]), float(g["weight_decay"]), ptr(self._ws),
+                 stream(), tag="adam_fold")
+            return
         bc1 = 1.0 - b1 ** self.step_count
         bc2 = 1.0 - b2 ** self.step_count
-        n = self.net
         call("harl_adam_fold", ptr(n.flat_param), ptr(n.flat_grad), ptr(self.exp_avg), ptr(self.exp_avg_sq), n.n_params,
              ptr(n.dwp), ptr(n.table), n.n_entries, ptr(n.pack_arena), ptr(n.scalars), ptr(part_scalars),
              int(n_scalar_blocks), ptr(scalars_hilo), int(mode), float(const_scale), int(logstd_off), int(act_dim), ptr(info_out),
              int(use_clip), float(max_norm), float(g["lr"]), float(b1), float(b2), float(g["eps"]),
              float(g["weight_decay"]), bc1, bc2, ptr(self._ws), stream(), tag="adam_fold")
+
+    HYPER_MIN_ROWS = 32
+
+    def begin_steps(self, n_steps: int) -> None:
+        """HARL_GRAPH=1, at the start of a train(): the host writes {lr, 1 - b1^t, 1 - b2^t} for t = step_count + 1 ...
+        (at least ``n_steps`` rows, the very Python doubles ``step`` hands to harl_adam_fold, from the CURRENT
+        param_groups[0]["lr"] -- update_linear_schedule keeps working) behind a zeroed step counter into a pinned buffer and
+        sends it to the device with one asynchronous copy on the update's stream.  Until end_steps() every step() launches
+        harl_adam_fold_dev, eagerly or from a replayed graph.  ``step_count`` stays the source of truth (state_dict, checkpoints).
+        Without a GPU only the host table is written and step() is unchanged."""
+        g = self.param_groups[0]
+        b1, b2 = g["betas"]
+        lr = float(g["lr"])
+        dev = self.net.flat_param.device
+        rows = max(int(n_steps), self.HYPER_MIN_ROWS)
+        if self._hyper_host is None or self._hyper_host.numel() < 1 + 3 * rows:
+            self._hyper_host = torch.zeros(1 + 3 * rows, dtype=torch.float64, pin_memory=dev.type == "cuda")
+            self._hyper_dev = torch.zeros(1 + 3 * rows, dtype=torch.float64, device=dev) if dev.type == "cuda" else None
+            self._hyper_ev = None
+        if self._hyper_ev is not None:  # (the previous copy out of this buffer: long done, one update ago)
+            self._hyper_ev.synchronize()
+        rows = (self._hyper_host.numel() - 1) // 3
+        h = self._hyper_host.numpy()
+        h[0] = 0.0  # the counter word: int32 zero in its first four bytes
+        for k in range(rows):
+            t = self.step_count + 1 + k
+            h[1 + 3 * k], h[2 + 3 * k], h[3 + 3 * k] = lr, 1.0 - b1 ** t, 1.0 - b2 ** t
+        if self._hyper_dev is None:
+            return
+        self._hyper_dev.copy_(self._hyper_host, non_blocking=True)
+        if self._hyper_ev is None:
+            self._hyper_ev = torch.cuda.Event()
+        self._hyper_ev.record()
+        self._hyper_base, self._hyper_rows = self.step_count, rows
+
+    def end_steps(self) -> None:
+        self._hyper_base = None
+
+    def hyper_rows_left(self) -> int:
+        """Steps the armed device table still covers (0: not armed)."""
+        return 0 if self._hyper_base is None else max(0, self._hyper_base + self._hyper_rows - self.step_count)
+
+    def hyper_table(self) -> torch.Tensor:
+        """The host table as written by the last begin_steps(): rows of {lr, bias_correction1, bias_correction2}."""
+        return self._hyper_host[1:].reshape(-1, 3)
 
     def state_dict(self) -> dict:
         return dict(step=self.step_count, exp_avg=self.exp_avg.clone(), exp_avg_sq=self.exp_avg_sq.clone(),
@@ -1239,6 +1327,7 @@ class FusedAdam:
 
     def load_state_dict(self, sd: dict) -> None:
         self.step_count = int(sd["step"])
+        self._hyper_base = None  # (a device table armed for the old step count)
         self.exp_avg.copy_(sd["exp_avg"])
         self.exp_avg_sq.copy_(sd["exp_avg_sq"])
         self.param_groups = [dict(g) for g in sd["param_groups"]]

@@ -391,6 +391,11 @@ class OnPolicyHARunner:
         critic_train_info = {"value_loss": flat[off], "critic_grad_norm": flat[off + 1]}
         return actor_train_infos, critic_train_info
 
+    def graph_stats(self) -> dict:
+        """Sum of the actors' and the critic's ``graph_stats()`` (HARL_GRAPH=1: captured / replayed / eager optimiser steps)."""
+        from .graphs import sum_stats
+        return sum_stats(list(self.actor) + [self.critic])
+
     def _critic_first_ok(self, fast) -> bool:
         """May the critic update be enqueued before the actors'?  Only when nothing in train() materialises a permutation
         (one full-buffer minibatch everywhere, feed-forward nets, HAPPO-family actors): then every sampler merely advances

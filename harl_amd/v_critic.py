@@ -6,7 +6,7 @@ from typing import Optional
 
 import torch
 
-from . import _lib
+from . import _lib, graphs
 from ._lib import PS_STRIDE, call, ptr, stream
 from .buffers import OnPolicyCriticBufferEP, consume_randperm, minibatch_indices, rng_sync
 from .dist import Comm, local_minibatch_rows
@@ -45,6 +45,18 @@ class VCritic:
         self._grad_tap = None
         self._trace = None  # test hook: snapshots of the running statistics after every optimiser step
         self._state_tap = None  # test hook: (parameters, exp_avg, exp_avg_sq, step) BEFORE every optimiser step
+        self._graph = graphs.GraphedStep("the critic")  # HARL_GRAPH=1: captured optimiser steps
+        self._graph_idx: Optional[torch.Tensor] = None  # persistent minibatch index buffer (a captured step holds addresses)
+        self._graph_gen = None
+
+    def graph_stats(self) -> dict:
+        """dict(captures, replays, eager_steps) of the critic's optimiser steps under HARL_GRAPH=1 (all zero without it)."""
+        return self._graph.stats()
+
+    def _graph_config_ok(self) -> bool:
+        """HARL_GRAPH=1 and a configuration whose optimiser steps may be replayed from a hipGraph (see HAPPO)."""
+        return (graphs.enabled() and not (self.use_recurrent_policy or self.use_naive_recurrent_policy)
+                and not self.critic.recurrent and not self.comm.enabled and self.shard is None)
 
     def lr_decay(self, episode, episodes):
         lr = self.critic_lr - (self.critic_lr * ((episode - 1) / float(episodes)))
@@ -83,9 +95,34 @@ class VCritic:
             out.copy_(outp.reshape(seq["L"], seq["m_pad"], 1)[:, :m].reshape(M, 1))
         return out, seq["h_last"][:m].reshape(m, net.recurrent_n, H).clone()
 
-    def _update_core(self, share_obs, idx, m, m_global, value_preds, returns, vn: Optional[ValueNorm], seq=None):
+    def _update_core(self, share_obs, idx, m, m_global, value_preds, returns, vn: Optional[ValueNorm], seq=None, _graph=False):
         """One optimiser step on rows idx[0..m) (m = 0: this rank holds none of the global minibatch's m_global rows and
-        only takes part in the collectives)."""
+        only takes part in the collectives).  ``_graph`` (HARL_GRAPH=1, graphs.py): replay the step from a hipGraph -- eager
+        all the same under a test hook or with instrumented launches."""
+        if not _graph:
+            return self._step(share_obs, idx, m, m_global, value_preds, returns, vn, seq)
+        G, net, opt = self._graph, self.critic, self.critic_optimizer
+        step = lambda: self._step(share_obs, idx, m, m_global, value_preds, returns, vn, seq)  # noqa: E731
+        if (seq is not None or m <= 0 or self._trace is not None or self._grad_tap is not None or self._state_tap is not None
+                or not graphs.launches_capturable(self.device) or opt.hyper_rows_left() < 1):
+            return G.eager(step)
+        net.prepare_x0n(share_obs, idx, m)  # the launch that depends on a host-side cache stays in front of the region
+        if self._graph_gen != net._ws_gen:
+            G.drop()
+            self._graph_gen = net._ws_gen
+        p = lambda t: 0 if t is None else t.data_ptr()  # noqa: E731
+        g = opt.param_groups[0]
+        e = os.environ.get
+        warm = (m, m_global, idx is None, vn is None, float(self.clip_param), bool(self.use_clipped_value_loss),
+                bool(self.use_huber_loss), float(self.huber_delta), float(self.value_loss_coef), bool(self.use_max_grad_norm),
+                float(self.max_grad_norm), tuple(g["betas"]), float(g["eps"]), float(g["weight_decay"]),
+                None if vn is None else vn.beta, e("HARL_FUSED_UPDATE"), e("HARL_BWD_FUSED"), e("HARL_BWD_K64"),
+                e("HARL_TRUNK_FUSED"))
+        key = warm + (p(share_obs), p(idx), p(value_preds), p(returns), None if vn is None else (p(vn.stats), p(vn._sums)),
+                      p(self._info), p(net.flat_param), p(net.pack_arena), p(opt.exp_avg), p(opt._hyper_dev), opt._hyper_rows)
+        G.run(warm, key, step, opt)
+
+    def _step(self, share_obs, idx, m, m_global, value_preds, returns, vn: Optional[ValueNorm], seq=None):
         net = self.critic
         s = stream()
         if vn is not None:  # ValueNorm.update runs on this minibatch's returns BEFORE the targets are normalised
@@ -197,6 +234,17 @@ class VCritic:
         value_preds = buf.flat("value_preds").reshape(B)
         returns = buf.flat("returns").reshape(B)
         n_global = self.shard[0] * T * (A or 1) if self.shard else B
+        graph = False
+        if self._graph_config_ok():  # HARL_GRAPH=1: the Adam scalars of the coming steps go to the device once (FusedAdam.begin_steps)
+            self.critic_optimizer.begin_steps(self.critic_epoch * self.critic_num_mini_batch)
+            graph = graphs.launches_capturable(dev)
+        try:
+            yield from self._epochs(buf, share_obs, value_preds, returns, value_normalizer, A, B, n_global, graph)
+        finally:
+            self.critic_optimizer.end_steps()
+
+    def _epochs(self, buf, share_obs, value_preds, returns, value_normalizer, A, B, n_global, graph: bool):
+        dev = self.device
         for _ in range(self.critic_epoch):
             if self.use_recurrent_policy or self.use_naive_recurrent_policy:
                 for seq in buf.recurrent_batches(self.critic_num_mini_batch, self.data_chunk_length,
@@ -211,7 +259,7 @@ class VCritic:
                 continue
             if self.critic_num_mini_batch == 1:
                 consume_randperm(n_global)  # replay the generator state only (see HAPPO.train)
-                self._update_core(share_obs, None, B, n_global, value_preds, returns, value_normalizer)
+                self._update_core(share_obs, None, B, n_global, value_preds, returns, value_normalizer, _graph=graph)
                 yield
                 continue
             sampler = minibatch_indices(n_global, self.critic_num_mini_batch, dev)
@@ -219,7 +267,12 @@ class VCritic:
                 m_global = ind.numel()
                 if self.shard:
                     ind = local_minibatch_rows(ind, self.shard[0], self.shard[1], self.shard[2], agents=A or 1)
-                self._update_core(share_obs, ind.to(dev), ind.numel(), m_global, value_preds, returns, value_normalizer)
+                if graph:  # every minibatch's rows go through ONE persistent index buffer (minibatches are of equal size)
+                    if self._graph_idx is None or self._graph_idx.shape != ind.shape or self._graph_idx.device != dev:
+                        self._graph_idx = torch.empty(ind.shape, dtype=ind.dtype, device=dev)
+                    self._graph_idx.copy_(ind)
+                self._update_core(share_obs, self._graph_idx if graph else ind.to(dev), ind.numel(), m_global, value_preds, returns,
+                                  value_normalizer, _graph=graph)
             yield
 
     def prep_training(self):

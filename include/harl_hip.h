@@ -11,7 +11,12 @@
  * Conventions
  *   - every pointer is a DEVICE pointer (memory owned by the caller, normally a torch tensor);
  *   - no allocation, no host synchronisation inside; work is enqueued on `stream`
- *     (a hipStream_t passed as void*), so calls are safe under hipGraph capture;
+ *     (a hipStream_t passed as void*).  A launch can therefore be captured into a hipGraph once every
+ *     kernel of the sequence has run eagerly in the process (the first call of a kernel with more than
+ *     64 KiB of LDS raises that limit, which is not a stream operation).  A replay repeats the captured
+ *     ARGUMENTS: a step whose host scalars change from step to step (harl_adam_fold: lr and the two bias
+ *     corrections) replays correctly only through the entry point that reads them from device memory
+ *     (harl_adam_fold_dev); harl_amd does this for its optimiser steps under HARL_GRAPH=1 (README);
  *   - return value: 0 on success, negative on error (harl_last_error() gives the text);
  *   - all floating data is fp32; "ATL" = activation tile layout: for a width-H
  *     activation, slab g (32 consecutive samples) is stored as [H/8][64 lanes][4] floats;
@@ -314,6 +319,18 @@ int harl_adam_fold(float *param, float *grad, float *exp_avg, float *exp_avg_sq,
                    int act_dim, double *info,
                    int use_clip, float max_norm, double lr, double beta1, double beta2, float eps, float weight_decay,
                    double bias_correction1, double bias_correction2, void *ws, void *stream);
+/* harl_adam_fold whose three per-step host scalars come from device memory, so that ONE captured launch can be replayed from a
+ * hipGraph step after step: hyper[n_hyper_rows][3] = {lr, bias_correction1, bias_correction2}, one row per upcoming step,
+ * filled by the HOST with the very doubles harl_adam_fold would be handed (lr; 1 - beta1^t; 1 - beta2^t: no pow on the
+ * device); step_idx[0] = row of this launch.  Every workgroup reads the counter on entry, one thread stores counter + 1
+ * behind the grid barrier; a counter past the table reads its last row.  Everything else -- arguments, arithmetic, results
+ * bit for bit -- is harl_adam_fold (same kernel body).  Replaces the same reference ops (happo.py:89-100, v_critic.py:144-155:
+ * torch.optim.Adam keeps `step` and `lr` on the host and recomputes both bias corrections per step). */
+int harl_adam_fold_dev(float *param, float *grad, float *exp_avg, float *exp_avg_sq, long n, const float *dwp,
+                       const int *table, int n_layers, float *packs, double *scalars, const float *part_scalars,
+                       int n_scalar_blocks, const float *scalars_hilo, int mode, float const_scale, int logstd_off,
+                       int act_dim, double *info, int use_clip, float max_norm, const double *hyper, int n_hyper_rows,
+                       int *step_idx, double beta1, double beta2, float eps, float weight_decay, void *ws, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Heads and losses.
