@@ -55,9 +55,10 @@ class OnPolicyBase:
 
     def _graph_config_ok(self) -> bool:
         """HARL_GRAPH=1 and a configuration whose optimiser steps may be replayed from a hipGraph: feed-forward, one action
-        head (Gaussian / Categorical), no data parallelism.  Everything else stays eager, exactly as without the variable."""
+        head (Gaussian / Categorical of up to 64 actions), no data parallelism.  Everything else stays eager, exactly as without
+        the variable."""
         return (graphs.enabled() and not (self.use_recurrent_policy or self.use_naive_recurrent_policy)
-                and not self.actor.recurrent and not self.actor.md and not self.comm.enabled and self.shard is None)
+                and not self.actor.recurrent and not self.actor.grouped and not self.comm.enabled and self.shard is None)
 
     def _graph_stage(self, name: str, t: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
         """Copy ``t`` into this actor's persistent buffer ``name`` (a captured step holds ADDRESSES)."""
@@ -82,10 +83,14 @@ class OnPolicyBase:
         resets.  Returns the final hidden state [m, H] when ``h_last`` is set."""
         net = self.actor
         agg = int(self.action_aggregation == "mean")
-        if net.md and not net.recurrent:  # MultiDiscrete: trunk -> logits of every group -> per-head log-softmax
+        if net.grouped and not net.recurrent:  # MultiDiscrete / wide Categorical: trunk -> logits of every group -> log-softmax
             if not reuse_trunk:
                 net.forward_trunk(obs, None, M, for_backward=False)
             net.md_logits(M)
+            if net.cat_wide:
+                call("harl_cat_head_logp", *net.cat_layout(), M, None, ptr(actions), ptr(avail), ptr(logp_out), None,
+                     ptr(old_logp), ptr(factor), ptr(head_out), 0, 0, stream(), tag="cat_head_logp")
+                return None
             call("harl_md_head_logp", *net.md_layout(), M, ptr(actions), ptr(logp_out), ptr(old_logp),
                  0 if old_logp is None else old_logp.shape[1], ptr(factor), agg, ptr(head_out), 0, 0, stream(),
                  tag="md_head_logp")
@@ -118,7 +123,11 @@ class OnPolicyBase:
         net.forward_trunk(obs, idx, Mp, for_backward=False, seq=seq)
         fx, _, _, fh = net.feat()
         Wp, bp = net._packs[-1]
-        if net.md:
+        if net.cat_wide:
+            net.md_logits(Mp)
+            call("harl_cat_head_logp", *net.cat_layout(), Mp, None, ptr(a_p), ptr(av_p), ptr(lo_p), None, ptr(old_p), ptr(f_p),
+                 ptr(ho_p), m, seq["m_pad"], stream(), tag="cat_head_logp")
+        elif net.md:
             net.md_logits(Mp)
             call("harl_md_head_logp", *net.md_layout(), Mp, ptr(a_p), ptr(lo_p), ptr(old_p),
                  0 if old_p is None else old_p.shape[1], ptr(f_p), agg, ptr(ho_p), m, seq["m_pad"], stream(),
@@ -303,6 +312,14 @@ class HAPPO(OnPolicyBase):
         fx, fmask, frstd, fh = net.feat()
         mv, mp = (seq["m"], seq["m_pad"]) if seq is not None else (0, 0)
         self._await_factor()
+        if net.cat_wide:  # Categorical of 65..512 actions (csrc/cathead.hip): as MultiDiscrete below, ONE softmax over the groups
+            net.md_logits(m)
+            nblk = _lib.load().harl_head_blocks(m)
+            call("harl_cat_head_loss", *net.cat_layout(), m, ptr(idx), ptr(actions), ptr(avail), ptr(old_logp), ptr(adv),
+                 ptr(adv_moments), ptr(factor), ptr(active), float(self.clip_param), float(self.entropy_coef),
+                 self._surrogate_mode, mv, mp, ptr(logp_out), ptr(net.part_scalars), nblk, s, tag="cat_head_loss")
+            net.backward_trunk(obs, idx, m, seq=seq)
+            return nblk
         if net.md:  # MultiDiscrete (csrc/multihead.hip): logits GEMM, per-sample loss -> d(logits) in place, layer-kernel backward
             net.md_logits(m)
             nblk = _lib.load().harl_head_blocks(m)
@@ -381,6 +398,8 @@ class HAPPO(OnPolicyBase):
                                           logp_out=logp_out)
             self._optimizer_step(nblk)
         if not _graph:
+            if self.actor.cat_wide and graphs.enabled():  # HARL_GRAPH=1: wide Categorical heads run eagerly, and say so
+                self._graph.eager_steps += 1
             return step()
         # HARL_GRAPH=1 (graphs.py): replay this step from a hipGraph.  Eager all the same: the epoch-0 step that also emits the
         # pre-update log-probs, steps under a test hook (they read back / clone between the launches), instrumented steps.

@@ -27,6 +27,9 @@ class HATRPO(OnPolicyBase):
     def __init__(self, args, obs_space, act_space, device=torch.device("cuda:0")):
         assert act_space.__class__.__name__ != "MultiDiscrete", \
             "only continuous and discrete action space is supported by HATRPO."
+        if act_space.__class__.__name__ == "Discrete" and int(act_space.n) > 64:
+            from .nets import CAT_WIDE_REFUSALS
+            raise NotImplementedError(CAT_WIDE_REFUSALS["hatrpo"] if int(act_space.n) <= 512 else CAT_WIDE_REFUSALS["n"])
         super().__init__(args, obs_space, act_space, device)
         self.kl_threshold = args["kl_threshold"]
         self.ls_step = args["ls_step"]

@@ -97,6 +97,8 @@ class MAPPO(HAPPO):
                     segs.append(None if ind is None else self._graph_stage(f"idx{a}", ind) if graph else ind.to(dev))
                 if graph and self._share_param_step_graphed(actor_buffer, segs, adv_a, moments, acc, A, B):
                     continue
+                if net.cat_wide and graphs.enabled():  # (HAPPO._update_core: eager under HARL_GRAPH=1, counted)
+                    self._graph.eager_steps += 1
                 acc.zero_()
                 net._ensure_ws(B)
                 net.scalars.zero_()

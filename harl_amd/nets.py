@@ -22,6 +22,7 @@ import torch.nn as nn
 from . import _lib
 from . import graphs as _graphs
 from ._lib import DHEAD_LD, PS_STRIDE, SLAB, call, ptr, stream
+from .configs import CAT_WIDE_REFUSALS
 
 SUPPORTED_WIDTHS = (64, 128, 256)
 # models_tools.py:28-50; ids of csrc/elementwise.hip (0 = the fused ReLU kernels)
@@ -138,7 +139,8 @@ class _FlatNet(nn.Module):
         self._x0n_key = None
         self._x0n_force = False  # build the image whatever the cache says (graphs.py: several buffers inside ONE captured step)
         self.md = False  # MultiDiscrete heads (StochasticPolicy)
-        self._md_sp: List[int] = []
+        self.cat_wide = False  # Categorical head of 65..512 actions, cut into groups of 128 rows (StochasticPolicy)
+        self._md_sp: List[int] = []  # image width of every head GROUP (MultiDiscrete / wide Categorical), empty otherwise
         self._cpu_params: List[Tuple[str, torch.Tensor]] = []
         self._build_trunk_params(args)
 
@@ -255,12 +257,20 @@ class _FlatNet(nn.Module):
                     ents.append((off(f"rnn.rnn.weight_ih_l{l}") + gate * H * H, off(f"rnn.rnn.bias_ih_l{l}") + gate * H, g, be, H, H))
                 for gate in range(3):
                     ents.append((off(f"rnn.rnn.weight_hh_l{l}") + gate * H * H, off(f"rnn.rnn.bias_hh_l{l}") + gate * H, -1, -1, H, H))
-        for (w, b, g, be, o, k) in layers[-nh:]:
-            ents.append((off(w), off(b), off(g), off(be), o, k))
+        for gi, (w, b, g, be, o, k) in enumerate(layers[-nh:]):
+            # wide Categorical: group gi = rows [128 gi, 128 gi + o) of the ONE contiguous head matrix (like the GRU gate blocks)
+            lo = 128 * gi if self.cat_wide else 0
+            ents.append((off(w) + lo * k, off(b) + lo, off(g), off(be), o, k))
         return ents
 
     def _head_names(self) -> Tuple[str, str, int]:
         raise NotImplementedError
+
+    @property
+    def grouped(self) -> bool:
+        """The head is one or more GROUPS of <= 128 logits (MultiDiscrete, Categorical of 65..512 actions): logits from
+        harl_mlp_linear into one image per group, backward through the layer kernels (md_logits / md_backward)."""
+        return bool(self._md_sp)
 
     def _build_tables(self) -> None:
         """Folded-weight arena, dense folded-gradient arena and the device layer table (include/harl_hip.h,
@@ -283,15 +293,15 @@ class _FlatNet(nn.Module):
             else:
                 if self.recurrent and ei == L:
                     pass
-                # MultiDiscrete group: the GEMM kernels read a full [sp][k] matrix (zero rows past the last head)
-                orows = self._md_sp[ei - (len(ents) - len(self._md_sp))] if (self.md and ei >= len(ents) - len(self._md_sp)) else o
+                # head group: the GEMM kernels read a full [sp][k] matrix (zero rows past the last head / action)
+                orows = self._md_sp[ei - (len(ents) - len(self._md_sp))] if (self.grouped and ei >= len(ents) - len(self._md_sp)) else o
                 pw, pb = pack_off, pack_off + orows * k
                 pack_off += orows * k + orows
                 if self.recurrent and ei == L - 1:  # reserve the GRU block right after the last MLP layer
                     self._gru_pack_base = pack_off
                     pack_off += 2 * self.recurrent_n * (3 * H * H + 3 * H)
             kp, op = ((k + 31) // 32) * 32, ((o + 31) // 32) * 32
-            if self.md and ei >= len(ents) - len(self._md_sp):
+            if self.grouped and ei >= len(ents) - len(self._md_sp):
                 op = self._md_sp[ei - (len(ents) - len(self._md_sp))]  # partial layout of harl_mlp_dw_partials(HO = sp)
             elems = op * kp + op
             rows.append([wo, bo, go, beo, o, k, pw, pb, dwp_off, kp, op, 0])
@@ -311,7 +321,7 @@ class _FlatNet(nn.Module):
         views = [(self.pack_arena[pw:pw + o * k], self.pack_arena[pb:pb + o]) for (pw, pb, o, k) in pack_slots]
         self._packs = views[:L] + [views[-1]]  # MLP layers by index, head last (callers use [l] and [-1])
         nh = len(self._head_layers())
-        self._head_packs = views[-nh:]          # every head entry (MultiDiscrete: one per group)
+        self._head_packs = views[-nh:]          # every head entry (MultiDiscrete / wide Categorical: one per group)
         if self.recurrent:
             n = 3 * H * H
             self.gru_packs = []  # per GRU layer: the folded [3H, H] gate matrices and [3H] biases
@@ -384,9 +394,9 @@ class _FlatNet(nn.Module):
         self.dz = [torch.empty(mp * hmax, dtype=f32, device=dev) for _ in range(3 if len(self.hidden_sizes) == 3 and self.trunk_fused() else 2)]
         self._trunk_cache = {}
         # head gradients for the separate dW pass: row-major [mp][32], or the ATL(64) image of a 33..64-way Categorical head
-        self.wide_head = (not self.md) and self._layers()[-1][4] > 32
+        self.wide_head = (not self.grouped) and self._layers()[-1][4] > 32
         self.dhead = torch.zeros(mp * (64 if self.wide_head else DHEAD_LD), dtype=f32, device=dev)
-        # MultiDiscrete: one logits image per group; the loss kernel overwrites it with d(loss)/d(logits)
+        # MultiDiscrete / wide Categorical: one logits image per group; the loss kernel overwrites it with d(loss)/d(logits)
         self.md_z = [torch.zeros(mp * sp, dtype=f32, device=dev) for sp in self._md_sp]
         n_iter = (n_slabs + 1) // 2
         # rows of the per-workgroup partial arena = grid of the weight-gradient kernels (two workgroups per CU: the measured
@@ -400,7 +410,7 @@ class _FlatNet(nn.Module):
         # head gradient, harl_mlp_bwd_dx_dw for the trunk): the other 256 rows would only be cleared by them and read back by
         # the combine (~22 MB each way per optimiser step at the 3-agent headline shapes)
         if (not nwg_env and _bwd_fused_mode(M) == "1" and len(self.hidden_sizes) >= 2 and all(h == 128 for h in self.hidden_sizes)
-                and ((self.in_dim + 31) // 32) * 32 == 32 and not (self.recurrent or self.md or self.act_id or self.panel)):
+                and ((self.in_dim + 31) // 32) * 32 == 32 and not (self.recurrent or self.grouped or self.act_id or self.panel)):
             nwg_cap = 256
         self.n_wg = max(1, min(nwg_cap, n_iter))
         part_off, rows = 0, [list(r) for r in self._table_rows]
@@ -627,7 +637,7 @@ class _FlatNet(nn.Module):
             return False
         if mode == "0" or (train and mode == "logp") or (train and mode == "actor" and isinstance(self, VNet)):
             return False
-        if not (not self.recurrent and not self.md and idx is None and seq is None
+        if not (not self.recurrent and not self.grouped and idx is None and seq is None
                 and len(hs) == 2 and hs[0] == hs[1] and hs[0] in (64, 128) and self.in_dim <= 64 and self._layers()[-1][4] <= 8):
             return False
         # ... and the launch must fit the LDS of one workgroup (the ACTOR step of a 128-wide network with 33..64 inputs does not:
@@ -641,7 +651,7 @@ class _FlatNet(nn.Module):
         Needs ReLU, equal 64 / 128-wide last two layers, a head of <= 8 outputs, and a layer kernel in front that stops
         before the last layer."""
         hs = self.hidden_sizes
-        if _fused_update_mode() != "hybrid" or self.act_id or self.recurrent or self.md or self.panel:
+        if _fused_update_mode() != "hybrid" or self.act_id or self.recurrent or self.grouped or self.panel:
             return False
         if seq is not None or len(hs) < 2 or hs[-1] != hs[-2] or hs[-1] not in (64, 128) or self._layers()[-1][4] > 8:
             return False
@@ -707,7 +717,7 @@ class _FlatNet(nn.Module):
         hdim = self._layers()[-1][4]
         fx, _, _, fh = self.feat()
         # head: dW_head' = dhead^T x_hat_L   (x_hat_L = GRU output for recurrent nets)
-        if self.md:
+        if self.grouped:
             self.md_backward(M)
         elif not head_dw_done:
             if self.wide_head:  # ATL(64) image: an ordinary two-operand weight-gradient GEMM (partial layout dWp[64][fh] | dbp[64])
@@ -922,7 +932,8 @@ class _FlatNet(nn.Module):
             main_s.wait_event(e1)
         self._combine_partials(s)
 
-    # ---- MultiDiscrete heads (csrc/multihead.hip): logits of every group from the head input; backward of the groups
+    # ---- grouped heads (MultiDiscrete: csrc/multihead.hip, Categorical of 65..512 actions: csrc/cathead.hip): logits of every
+    # group from the head input; backward of the groups
     def md_logits(self, M: int) -> None:
         fx, _, _, fh = self.feat()
         s = stream()
@@ -936,8 +947,15 @@ class _FlatNet(nn.Module):
         zs = (C.c_void_p * G)(*[z.data_ptr() for z in self.md_z])
         return (zs, G, (C.c_int * G)(*self._md_sp), K, (C.c_int * K)(*self.nvec), (C.c_int * K)(*self._md_head_group))
 
+    def cat_layout(self):
+        """(z pointer array, n_groups, sp[], n) -- the leading arguments of harl_cat_head_*."""
+        import ctypes as C
+        G = len(self._md_sp)
+        zs = (C.c_void_p * G)(*[z.data_ptr() for z in self.md_z])
+        return (zs, G, (C.c_int * G)(*self._md_sp), self.act_dim)
+
     def md_backward(self, M: int) -> None:
-        """d(loss)/d(logits) images (self.md_z, written by harl_md_head_loss) -> the groups' weight-gradient partials and
+        """d(loss)/d(logits) images (self.md_z, written by harl_md_head_loss / harl_cat_head_loss) -> the groups' weight-gradient partials and
         d(loss)/d(head input) in self.dz[0]: the layer kernels of a hidden Linear (sum over the groups)."""
         fx, fmask, frstd, fh = self.feat()
         s = stream()
@@ -1010,11 +1028,29 @@ class StochasticPolicy(_FlatNet):
             self._init_multidiscrete(args, action_space, init, d)
         else:
             raise NotImplementedError(f"action space {self.action_type}")
-        if not self.md and (self.act_dim > 64 or (self.act_dim > 32 and not self.discrete)):
+        if self.action_type == "Discrete" and self.act_dim > 64:
+            self._init_cat_wide()
+        if not self.grouped and (self.act_dim > 64 or (self.act_dim > 32 and not self.discrete)):
             raise NotImplementedError("action heads wider than 32 (Categorical: 64) are not instantiated")
-        self.wide_head = (not self.md) and self.act_dim > 32
+        self.wide_head = (not self.grouped) and self.act_dim > 32
         self._finalize_params()
         self.fold()
+
+    def _init_cat_wide(self) -> None:
+        """Categorical(hidden, n) with 65 <= n <= 512 (csrc/cathead.hip).  The parameters are the reference's ONE [n, H] matrix
+        and [n] bias (registered above: same names, order and RNG draws); the kernels see its rows in groups of 128 -- group g =
+        rows [128 g, min(128 (g + 1), n)), one table entry, folded pack, logits image and weight-gradient partial block each;
+        the last group is an ATL(64) image when it holds <= 64 rows."""
+        n = self.act_dim
+        if n > 512:
+            raise NotImplementedError(CAT_WIDE_REFUSALS["n"])
+        if self.panel:
+            raise NotImplementedError(CAT_WIDE_REFUSALS["panel"])
+        if self.act_id:
+            raise NotImplementedError(CAT_WIDE_REFUSALS["act"])
+        self.cat_wide = True
+        self._cat_rows = [min(128, n - lo) for lo in range(0, n, 128)]
+        self._md_sp = [64 if r <= 64 else 128 for r in self._cat_rows]
 
     def _init_multidiscrete(self, args: dict, action_space, init, d: int) -> None:
         """Heads in the reference's order (same RNG draws), packed first-fit IN ORDER into groups of <= 128 logits; a group is
@@ -1060,6 +1096,9 @@ class StochasticPolicy(_FlatNet):
         self._hidden_blocks, self._alias_params = tuple(hidden), alias
 
     def _head_layers(self):
+        if self.cat_wide:  # the groups are row ranges of the one head matrix (_entries adds the row offset)
+            w, b, _ = self._head_names()
+            return [(w, b, r) for r in self._cat_rows]
         if self.md:
             return [(f"__md{g}.weight", f"__md{g}.bias", sum(self.nvec[k] for k in ks)) for g, ks in enumerate(self._md_groups)]
         return [self._head_names()]

@@ -98,6 +98,24 @@ def _gru_bwd(a: Sequence) -> float:
     return L * m_pad * (6 * 4.0 * H + 4.0 + _act(H) + 4 * 4.0 * H + 4.0 * H)
 
 
+def _cat_head_logp(a: Sequence) -> float:
+    # (z, n_groups, sp, n, M, idx, actions, avail, logp_out, ent_out, old_logp, factor, head_out, m_valid, m_pad, stream): every
+    # logits image once (the second pass re-reads it only to emit head_out), the availability row, the per-row scalars
+    G, n, M = a[1], a[3], a[4]
+    row = 4.0 * sum(a[2][g] for g in range(G)) + (4.0 * n if a[7] else 0.0) + (8.0 if a[5] else 0.0)
+    row += sum(4.0 for k in (6, 8, 9, 10) if a[k]) + (8.0 if a[11] else 0.0) + (4.0 * n if a[12] else 0.0)
+    return M * row
+
+
+def _cat_head_loss(a: Sequence) -> float:
+    # (z, n_groups, sp, n, M, idx, actions, avail, old_logp, adv, adv_moments, factor, active, clip_param, entropy_coef, mode,
+    #  m_valid, m_pad, logp_out, part_scalars, n_blocks, stream): every image read once and overwritten with its gradient
+    G, n, M = a[1], a[3], a[4]
+    row = 2 * 4.0 * sum(a[2][g] for g in range(G)) + (4.0 * n if a[7] else 0.0) + (8.0 if a[5] else 0.0)
+    row += 3 * 4.0 + sum(4.0 for k in (11, 12, 18) if a[k])  # actions, old_logp, adv + factor, active, logp_out
+    return M * row
+
+
 def _nonnull(arr) -> int:
     return sum(1 for p in arr if p)
 
@@ -245,6 +263,8 @@ ALGORITHMIC_BYTES: Dict[str, Callable[[Sequence], float]] = {
     "harl_gae_returns": _gae,
     "harl_mlp_panel_fwd": _panel_fwd,
     "harl_mlp_panel_bwd": _panel_bwd,
+    "harl_cat_head_logp": _cat_head_logp,
+    "harl_cat_head_loss": _cat_head_loss,
     "harl_mlp_tangent_hidden": _tangent_hidden,
     "harl_mlp_tangent_hidden2": _tangent_hidden,  # (same leading arguments: xin_dot, xin, M, HI, HO)
 }

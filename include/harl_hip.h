@@ -529,6 +529,32 @@ int harl_md_head_loss(const float *const *z, float *const *dz, int n_groups, con
                       long m_pad, float *logp_out, float *part_scalars, int n_blocks, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Categorical heads of 65..512 actions (harl/models/base/act.py:24-43,45-86,104-157 with distributions.py:7-25,37-55:
+ * Categorical(hidden, n) of a Discrete(n) space and its availability mask; csrc/cathead.hip).  The head's n rows are cut into
+ * n_groups = ceil(n / 128) GROUPS, group g = rows [128 g, min(128 (g + 1), n)) as one weight block Wp_g [sp_g][H] (sp_g = 128,
+ * the last group 64 when it holds <= 64 rows; zero rows past n), with logits, weight gradients and trunk gradient from
+ * harl_mlp_linear / harl_mlp_dw_partials / harl_mlp_bwd_dx exactly as for the MultiDiscrete groups above.  z: HOST array of
+ * n_groups device pointers to the ATL(sp_g) logits images.  ONE softmax spans the groups: logits of unavailable actions
+ * (avail [rows, n] == 0; NULL = none) are -1e10 before the maximum, rows >= n of the last image are ignored.  idx (nullable)
+ * gathers actions / avail (and, in the loss, every per-row input) by row; outputs are addressed by batch position.
+ * harl_cat_head_logp (forward of evaluate_actions / get_actions, act.py:45-86,143-157): any of the outputs may be NULL --
+ *   logp_out[M] = log pi(a), ent_out[M] = entropy per row, head_out[M, n] = the normalised logits (input of harl_dist_rows);
+ *   if factor != NULL: factor[i] *= exp(logp - old_logp[i]) (on_policy_ha_runner.py:116-124).
+ * harl_cat_head_loss (happo.py:66-91, haa2c.py:70-80 through autograd of the Categorical): the statistics above, importance
+ *   ratio against old_logp[rows], clipped surrogate x factor (mode 0; mode 2 = HAA2C, unclipped), active-mask-weighted entropy
+ *   bonus -- aggregation, active masks and entropy normalisation exactly those of the Discrete branch of
+ *   harl_actor_head_loss -- and d(unscaled loss)/d(logits) written IN PLACE into the images (0 in rows >= n and for samples
+ *   past M / padding sequences).  part_scalars[n_blocks][HARL_PS_STRIDE] as harl_actor_head_loss
+ *   ({0: sum loss*active, 1: sum active, 2: sum ent*active, 3: sum ratio, 4: count}); launched with n_blocks workgroups. */
+int harl_cat_head_logp(const float *const *z, int n_groups, const int *sp, int n, long M, const int64_t *idx,
+                       const float *actions, const float *avail, float *logp_out, float *ent_out, const float *old_logp,
+                       float *factor, float *head_out, long m_valid, long m_pad, void *stream);
+int harl_cat_head_loss(float *const *z, int n_groups, const int *sp, int n, long M, const int64_t *idx, const float *actions,
+                       const float *avail, const float *old_logp, const float *adv, const double *adv_moments,
+                       const float *factor, const float *active, double clip_param, float entropy_coef, int mode,
+                       long m_valid, long m_pad, float *logp_out, float *part_scalars, int n_blocks, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Fused optimiser-step kernels for two equal-width hidden layers (H in {64, 128}) and inputs up to 64 wide, identity
  * row order (csrc/update.hip).  They take the cached normalised-input image x0n (harl_mlp_x0n_wide) and keep every
  * activation on chip: x_hat_1, x_hat_2, the ReLU masks and LayerNorm statistics are never written; x_hat_1 is recomputed
