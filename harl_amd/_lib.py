@@ -41,6 +41,7 @@ SIGNATURES = {
     "harl_unfold_linear_grads": [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp],
     "harl_mlp_fwd_input": [_vp, _l, _vp, _l, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "harl_mlp_x0n_wide": [_vp, _l, _vp, _l, _i, _i, _vp, _vp, _vp, _vp],
+    "harl_x0n_multi": [_vp, _i, _i, _vp],
     "harl_mlp_fwd_wide": [_vp, _l, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp],
     "harl_mlp_linear_wide": [_vp, _l, _i, _vp, _i, _vp, _i, _vp, _vp, _vp],
     "harl_act_ln_fwd": [_vp, _l, _i, _i, _vp, _vp, _vp, _vp],
@@ -242,6 +243,42 @@ def call(name: str, *args, tag: Optional[str] = None) -> None:
         rc = fn(*args)
     if rc != 0:
         raise RuntimeError(f"{name} failed ({rc}): {load().harl_last_error().decode()}")
+
+
+X0N_MULTI_MAX = 32  # include/harl_hip.h: HARL_X0N_MULTI_MAX
+
+
+class X0nProblem(C.Structure):
+    """harl_x0n_problem (include/harl_hip.h): one network's image in the one-launch harl_x0n_multi."""
+    _fields_ = [("X", _vp), ("ldx", _l), ("M", _l), ("D", _i), ("use_ln0", _i), ("x0n", _vp), ("mu0", _vp), ("rstd0", _vp)]
+
+
+def x0n_multi(problems, max_workgroups: int = 0, tag: Optional[str] = "x0n_multi") -> bool:
+    """``harl_x0n_multi`` over ``problems`` = [(X ptr, ldx, M, D, use_ln0, x0n ptr, mu0 ptr, rstd0 ptr), ...] on the current
+    stream.  False = the library does not take this set in one launch (nothing was launched: the caller takes the per-network
+    launches); a failed launch raises as every other entry point does."""
+    if not 1 <= len(problems) <= X0N_MULTI_MAX:
+        return False
+    table = (X0nProblem * len(problems))(*[X0nProblem(*p) for p in problems])
+    fn = _fn_cache.get("harl_x0n_multi")
+    if fn is None:
+        fn = _fn_cache["harl_x0n_multi"] = load().harl_x0n_multi
+    timed = _timing_on and tag is not None and (_timing_tags is None or tag in _timing_tags)
+    if timed:
+        a = _event_pool.pop() if _event_pool else torch.cuda.Event(enable_timing=True)
+        b = _event_pool.pop() if _event_pool else torch.cuda.Event(enable_timing=True)
+        a.record()
+    rc = fn(table, len(problems), max_workgroups, stream())
+    if rc == 1:
+        return False
+    if rc != 0:
+        raise RuntimeError(f"harl_x0n_multi failed ({rc}): {load().harl_last_error().decode()}")
+    if timed:
+        b.record()
+        # (bytes: every row read once, the image and the two statistics written once)
+        nb = sum(4 * ((p[2] + 31) // 32 * 32) * (p[3] + (p[3] + 31) // 32 * 32 + 2) for p in problems)
+        _timing_events.setdefault(tag, []).append((a, b, nb, 0.0))
+    return True
 
 
 SCRATCH_BYTES = {"mm": 24640, "cg": 1088}  # include/harl_hip.h: HARL_MM_SCRATCH_BYTES, HARL_CG_SCRATCH_BYTES

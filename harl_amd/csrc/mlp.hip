@@ -1614,6 +1614,16 @@ extern "C" int harl_mlp_bwd_dx(const float *dz, const float *xprev, const uint32
   return check_launch("harl_mlp_bwd_dx");
 }
 
+// What `fill = 1` (the callers' default) launches; 2 forces the fillers, 0 forbids them.  With ONE wave per SIMD (-DHARL_BWD_SPLIT_WAVES=0) the operand splits
+// pinned into the MFMA shadows of the weight-gradient rounds win (0.4393 against 0.4622 ms per launch at 819 200 rows); with
+// TWO waves per SIMD the partner wave fills those shadows by itself and the pinned slots only constrain the schedule
+// (profiles/r07_bwd_split_waves_ab.md, profiles/r10_update_trims.md).  Same arithmetic in the same order: bit-identical.
+#if HARL_BWD_SPLIT_WAVES
+constexpr bool BDW_FILL_FIRST = false, BDW_FILL_HIDDEN = false;
+#else
+constexpr bool BDW_FILL_FIRST = true, BDW_FILL_HIDDEN = true;
+#endif
+
 extern "C" int harl_mlp_bwd_dx_dw(const float *dz, const float *xprev, const uint32_t *relu_mask_prev,
                                   const float *rstd_prev, long M, int HO, int HI, const float *Wp, float *dz_prev,
                                   const float *x0n, int kp0, float *dw1_part, float *dw2_part, int n_wg, int fill,
@@ -1645,8 +1655,10 @@ extern "C" int harl_mlp_bwd_dx_dw(const float *dz, const float *xprev, const uin
                        rstd_prev, Wp, dz_prev, n_slabs, x0n, dw1_part, dw2_part, n_wg);                              \
   }
 #endif
-  if (first) { if (fill) LB(1, true) else LB(1, false) }
-  else { if (fill) LB(0, true) else LB(0, false) }
+  // fill = 1 (what callers pass by default): the build's own choice per variant, BDW_FILL_FIRST / BDW_FILL_HIDDEN above
+  const bool fl = fill == 1 ? (first ? BDW_FILL_FIRST : BDW_FILL_HIDDEN) : fill != 0;
+  if (first) { if (fl) LB(1, true) else LB(1, false) }
+  else { if (fl) LB(0, true) else LB(0, false) }
 #undef LB
   return check_launch("harl_mlp_bwd_dx_dw");
 }

@@ -87,6 +87,7 @@ def _runner_class(base_cls, ours):
         _init_update_state = ours._init_update_state
         _ensure_update_state = ours._ensure_update_state
         _critic_first_ok = getattr(ours, "_critic_first_ok", None)
+        _prepare_inputs = ours._prepare_inputs
         _fp_normalised_advantages = ours._fp_normalised_advantages
         _check_comms = ours._check_comms
         warmup = ours.warmup

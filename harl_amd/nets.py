@@ -47,16 +47,41 @@ def _bwd_fused_mode(M: int = 0) -> str:
     """``HARL_BWD_FUSED``: "auto" (default) = 128 x 128 hidden layers take harl_mlp_bwd_dx_dw (dx + the layer's weight gradient +
     the fused first-layer one in ONE launch, operand splits interleaved with the MFMAs: dz and x_hat cross HBM once) when the
     minibatch has at least BWD_FUSED_MIN_ROWS rows, the layer kernels (harl_mlp_dw_partials + harl_mlp_bwd_dx) below that;
-    "1" / "0" force one or the other; "nofill" = the one-launch kernel with the splits in separate phases (A/B).
+    "1" / "0" force one or the other; "nofill" / "fill" = the one-launch kernel with the operand splits in separate phases /
+    pinned into the MFMA shadows of the weight-gradient rounds (A/B; "1" and "auto" leave that to the library, which takes the
+    faster one per build and variant: no fillers at two waves per SIMD, profiles/r10_update_trims.md).
     Measured on MI355X (profiles/r05_bwd_fused_ab.md): 17 % fewer HBM bytes per MPE step at the SAME step time (17.09 ms both),
     -2.5 % on the 6-agent three-layer workload (819 200 rows per launch); at 204 800 rows (6.25 super-rounds per workgroup, the
     weight staging and the pipeline's first round amortised over too few slabs) it is 1.5 % slower -- hence the threshold."""
     m = os.environ.get("HARL_BWD_FUSED", "auto")
-    if m not in ("0", "1", "nofill", "auto"):
-        raise ValueError(f"HARL_BWD_FUSED={m!r}: expected auto, 0, 1 or nofill")
+    if m not in ("0", "1", "nofill", "fill", "auto"):
+        raise ValueError(f"HARL_BWD_FUSED={m!r}: expected auto, 0, 1, nofill or fill")
     if m == "auto":
         return "1" if M >= BWD_FUSED_MIN_ROWS else "0"
     return m
+
+
+def prepare_x0n_multi(items) -> int:
+    """Head of a feed-forward update: the normalised-input images of several networks -- ``items`` = [(net, X, M), ...], every
+    actor's observations and the critic's -- in ONE launch on the current stream (harl_x0n_multi, csrc/wide.hip) instead of one
+    launch per network where each is first read, each behind the host work in front of that network's update.  The images
+    depend on the observation buffers only, which nothing writes during train().  Every image goes into its network's own
+    cache under the key _x0n_image would give it, so the later fused_args() / forward_trunk() calls find it and launch
+    nothing, and it is dropped with the next invalidate_caches() as ever.  Networks the launch does not cover (x0n_multi_item)
+    and everything under HARL_X0N_MULTI=0 or a graph capture keep the lazy per-network launch.  Returns the number of images built."""
+    if os.environ.get("HARL_X0N_MULTI", "1") == "0" or _graphs.enabled():
+        return 0
+    todo = []
+    for net, X, M in items:
+        it = net.x0n_multi_item(X, M)
+        if it is not None and it[0] != net._x0n_key and not net._x0n_force:  # (forced: rebuilt at every use anyway)
+            todo.append((net, X, it))
+    todo = todo[:_lib.X0N_MULTI_MAX]
+    if not todo or not _lib.x0n_multi([it[1] for _, _, it in todo]):
+        return 0
+    for net, X, it in todo:
+        net._x0n_key, net._x0n_src = it[0], (X, None)
+    return len(todo)
 
 
 def _bwd_streams() -> bool:
@@ -526,6 +551,24 @@ class _FlatNet(nn.Module):
         else:
             self._x0n_key = None  # harl_mlp_fwd_input may write self.x0n
 
+    def x0n_multi_item(self, X: torch.Tensor, M: int):
+        """This network's entry in a one-launch build of several images (prepare_x0n_multi): (cache key, problem tuple of
+        _lib.x0n_multi) when a full-buffer, identity-order pass over ``X`` reads the image that harl_mlp_x0n_wide(X, idx =
+        None) builds and the one-launch kernel covers it (dense rows up to 64 wide) -- None otherwise, and the image is built
+        where it is first asked for (recurrent nets, wider inputs, routes without an image, an empty data-parallel shard)."""
+        hs = self.hidden_sizes
+        if self.recurrent or M < 1 or not 1 <= self.in_dim <= 64 or X.dim() != 2 or X.shape[1] != self.in_dim or not X.is_contiguous():
+            return None
+        two_equal = len(hs) >= 2 and hs[0] == hs[1]
+        if not (self.act_id or self.panel or self.trunk_fused() or two_equal or self.wide):  # the routes of prepare_x0n
+            return None
+        self._ensure_ws(M)
+        if self.x0n is None:
+            return None
+        key = (X.data_ptr(), X._version, tuple(X.shape), M)  # == _x0n_image's for idx None
+        return key, (ptr(X), self.in_dim, M, self.in_dim, int(self.use_feature_normalization), ptr(self.x0n), ptr(self.mu0),
+                     ptr(self.rstd0))
+
     def invalidate_caches(self) -> None:
         """Drop the cached normalised-input image.  The cache key is (data_ptr, torch version counter, shape, rows): it
         sees in-place torch writes but NOT writes through ``.data``, DLPack / NumPy-shared memory or raw-pointer kernels.
@@ -802,7 +845,7 @@ class _FlatNet(nn.Module):
                 call("harl_mlp_bwd_dx_dw", ptr(self.dz[cur]), ptr(self.xh[l - 1]), ptr(self.rmask[l - 1]), ptr(self.rstd[l - 1]), M,
                      ho, hi, ptr(Wp), None if dw1_here else ptr(self.dz[1 - cur]), ptr(self.x0n) if dw1_here else None,
                      self.kp0 if dw1_here else 0, ptr(self.part[po[0]:]) if dw1_here else None, ptr(self.part[po[l]:]), nwg,
-                     int(bwd_mode != "nofill"), s, tag="bwd_full_dw1" if dw1_here else "bwd_full")
+                     {"nofill": 0, "fill": 2}.get(bwd_mode, 1), s, tag="bwd_full_dw1" if dw1_here else "bwd_full")
                 cur = 1 - cur
                 continue
             # HARL_BWD_STREAMS=1: the layer's weight gradient goes to a SECOND stream, next to the backward-dx launch -- both read

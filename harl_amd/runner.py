@@ -150,6 +150,7 @@ class OnPolicyHARunner:
         actor_train_infos = []
         for x in self.actor:  # cached normalised-input images never outlive one update (nets.invalidate_caches)
             x.actor.invalidate_caches()
+        self._prepare_inputs()
         factor = torch.ones(T, N, 1, dtype=torch.float32, device=dev)
         advantages = self.critic_buffer.advantages  # returns[:-1] - denormalize(value_preds[:-1]), fused into the GAE scan
         if self.state_type == "FP":
@@ -300,6 +301,8 @@ class OnPolicyHARunner:
         # results.  HARL_POST_STREAM=0 keeps the pass on the main stream.
         post_ok = dev.type == "cuda" and os.environ.get("HARL_POST_STREAM", "1") != "0"
         factor_ev, keep_alive, prev_overlapped = None, [], False
+        # (device "cpu" exists under the tests' launch recorder only, which pins the reference's one pass per agent)
+        last_post = os.environ.get("HARL_LAST_POST_PASS", "0") == "1" or dev.type != "cuda"
         for pos, agent_id in enumerate(agent_order):
             buf, actor = self.actor_buffer[agent_id], self.actor[agent_id]
             if agent_id in old_ev:  # this agent's networks / workspaces are in use on the side stream until then
@@ -343,6 +346,10 @@ class OnPolicyHARunner:
             actor_train_infos.append(info)
             nxt = agent_order[pos + 1] if pos + 1 < len(agent_order) else None
             prev_overlapped = bool(post_ok and nxt is not None and actor.actor.recurrent and hasattr(self.actor[nxt], "_factor_ready"))
+            if nxt is None and not last_post:
+                # the factor behind the LAST agent of the order is handed to nobody (on_policy_ha_runner.py:96-124 computes it
+                # and drops it): no clone, no forward over the whole batch.  HARL_LAST_POST_PASS=1 runs it all the same.
+                continue
             if prev_overlapped:
                 if getattr(self, "_post_stream", None) is None:
                     self._post_stream = torch.cuda.Stream(device=dev)
@@ -390,6 +397,36 @@ class OnPolicyHARunner:
                 off += len(keys)
         critic_train_info = {"value_loss": flat[off], "critic_grad_norm": flat[off + 1]}
         return actor_train_infos, critic_train_info
+
+    def _prepare_inputs(self) -> None:
+        """Head of train(): every feed-forward network's folded weights (one harl_fold_table each) and then ALL their
+        normalised-input images in ONE launch (nets.prepare_x0n_multi), enqueued back to back before the first agent's
+        update.  Lazily, each network built its image where its update first read it, a latency-bound launch behind the host
+        work at the head of that update (0.19 ms of idle GPU in front of the critic's, profiles/r06s3_kernel_trace_mpe.md).
+        Neither depends on anything train() computes: a network's parameters change in its own update only, the observation
+        buffers not at all.  Same kernels' arithmetic, same operands: bit-identical.  The critic's entry invalidation happens
+        here instead of in VCritic._train_epochs (told through ``_inputs_prepared``), so its image lives for this train() as
+        before.  Networks that are not covered -- recurrent, several minibatches (gathered rows), inputs wider than 64, an
+        empty data-parallel shard, HARL_GRAPH=1 -- keep the lazy launches; HARL_X0N_MULTI=0 keeps them everywhere."""
+        from . import graphs
+        if os.environ.get("HARL_X0N_MULTI", "1") == "0" or self.device.type != "cuda" or graphs.enabled():
+            return
+        from .nets import prepare_x0n_multi
+        items = []
+        for a, buf in zip(self.actor, self.actor_buffer):
+            if hasattr(a, "fuses_old_logp") and a.fuses_old_logp():
+                items.append((a.actor, buf.flat("obs")))
+        c = self.critic
+        crit = (c.critic_num_mini_batch == 1 and not (c.use_recurrent_policy or c.use_naive_recurrent_policy)
+                and hasattr(c, "_inputs_prepared"))
+        if crit:
+            c.critic.invalidate_caches()
+            items.append((c.critic, self.critic_buffer.flat("share_obs")))
+        for net, _ in items:
+            net.fold()
+        built = prepare_x0n_multi([(net, X, X.shape[0]) for net, X in items])
+        if crit and built:
+            c._inputs_prepared = True  # (consumed by the critic's train(): it does not invalidate again)
 
     def graph_stats(self) -> dict:
         """Sum of the actors' and the critic's ``graph_stats()`` (HARL_GRAPH=1: captured / replayed / eager optimiser steps)."""

@@ -41,6 +41,7 @@ class VCritic:
         self.critic_optimizer = FusedAdam(self.critic, self.critic_lr, self.opti_eps, self.weight_decay)
         self.comm = Comm()
         self.shard = None
+        self._inputs_prepared = False  # set by the runner's train() when it has built this update's input image up front
         self._info = torch.zeros(2, dtype=torch.float64, device=self.device)  # fp64 sums of the per-update fp32 value_loss, critic_grad_norm (v_critic.py:186-187)
         self._grad_tap = None
         self._trace = None  # test hook: snapshots of the running statistics after every optimiser step
@@ -227,7 +228,10 @@ class VCritic:
         B = T * N * (A or 1)
         dev = self.device
         self._info.zero_()
-        self.critic.invalidate_caches()
+        if self._inputs_prepared:  # the runner invalidated at ITS entry and built this update's image (runner._prepare_inputs)
+            self._inputs_prepared = False
+        else:
+            self.critic.invalidate_caches()
         buf.__dict__.pop("_seq_cache", None)  # the recurrent samplers' per-update table never outlives one train() (buffers._recurrent_seqs)
         self.critic.fold()
         share_obs = buf.flat("share_obs")

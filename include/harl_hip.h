@@ -158,6 +158,21 @@ int harl_mlp_fwd_input(const float *X, long ldx, const int64_t *idx, long M, int
  *     bf16 images of Wp, rebuilt on every call). */
 int harl_mlp_x0n_wide(const float *X, long ldx, const int64_t *idx, long M, int D, int use_ln0, float *x0n, float *mu0,
                       float *rstd0, void *stream);
+/* The images of SEVERAL networks in ONE launch (every actor's and the critic's at the head of a feed-forward update: the
+ * observation buffers do not change while the update runs).  `table`: n <= HARL_X0N_MULTI_MAX problems in HOST memory (read
+ * during the call; it travels as the kernel's argument).  Each problem is what harl_mlp_x0n_wide(X, ldx, NULL, M, D, use_ln0,
+ * x0n, mu0, rstd0) computes, bit for bit.  Only dense identity-order rows up to 64 wide (ldx == D, 1 <= D <= 64, M >= 1, no
+ * NULL pointer) are supported: anything else returns 1 WITHOUT launching and the caller takes the per-network launches.
+ * Workgroup ranges are dealt to the problems in proportion to their slab counts, a slab of rows wider than 32 counting four
+ * (its measured cost), at least one each; max_workgroups: the launch's budget (0 = 1024, four per CU). */
+#define HARL_X0N_MULTI_MAX 32
+typedef struct {
+  const float *X;
+  long ldx, M;
+  int D, use_ln0;
+  float *x0n, *mu0, *rstd0;
+} harl_x0n_problem;
+int harl_x0n_multi(const harl_x0n_problem *table, int n, int max_workgroups, void *stream);
 int harl_mlp_fwd_wide(const float *x0n, long M, int KP, const float *Wp, int D, const float *bp, int H, void *w_img,
                       float *xout, uint32_t *relu_mask, float *rstd, void *stream);
 /* Hidden width 256 (csrc/panel.hip; the reference's dexhands HAPPO configurations, mlp.py:7-70 with hidden_sizes
@@ -212,8 +227,10 @@ int harl_mlp_bwd_dx(const float *dz, const float *xprev, const uint32_t *relu_ma
  * i.e. harl_mlp_dw_partials(dz, xprev) + harl_mlp_bwd_dx(...) with dz and xprev read from HBM ONCE.  dw2_part: n_wg partial rows
  * [HO*HI + HO] in the layout of harl_mlp_dw_partials (the launch uses min(n_wg, 256) of them and clears the rest).
  * dw1_part != NULL: FIRST-layer variant as in harl_mlp_bwd_dx (x0n = ATL(32) image, kp0 = 32; dz_prev may be NULL);
- * dw1_part == NULL: dz_prev (ATL(HI)) is written.  fill: 1 = the operand splits are interleaved with the MFMAs of the
- * weight-gradient rounds (default), 0 = the same work in separate phases (A/B measurements).  HO = HI = 128 only. */
+ * dw1_part == NULL: dz_prev (ATL(HI)) is written.  fill: 2 = the operand splits are interleaved with the MFMAs of the
+ * weight-gradient rounds, 0 = the same work in separate phases, 1 (the default) = whichever of the two measured faster for
+ * this build and variant: separate phases at two waves per SIMD, interleaved with -DHARL_BWD_SPLIT_WAVES=0.  All three agree
+ * bit for bit.  HO = HI = 128 only. */
 int harl_mlp_bwd_dx_dw(const float *dz, const float *xprev, const uint32_t *relu_mask_prev, const float *rstd_prev,
                        long M, int HO, int HI, const float *Wp, float *dz_prev, const float *x0n, int kp0, float *dw1_part,
                        float *dw2_part, int n_wg, int fill, void *stream);

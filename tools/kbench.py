@@ -65,6 +65,10 @@ def main():
     part_h = torch.empty(n_wg * (32 * H + 32), device=dev)
     part_1 = torch.empty(n_wg * (H * 32 + H), device=dev)
     s = stream()
+    # the MPE update's head: three actors' observations and the critic's, each with buffers of its own, in ONE launch
+    multi_bufs = [(rn(B, 18), torch.empty(mp * 32, device=dev), torch.empty(mp, device=dev), torch.empty(mp, device=dev)) for _ in range(3)]
+    multi_bufs.append((rn(B, 54), torch.empty(mp * 64, device=dev), torch.empty(mp, device=dev), torch.empty(mp, device=dev)))
+    multi_problems = [(ptr(x), x.shape[1], B, x.shape[1], 1, ptr(im), ptr(mu), ptr(rs)) for x, im, mu, rs in multi_bufs]
     GF = lambda f: ("TFLOP/s", f / 1e12)  # noqa: E731
     GB = lambda f: ("TB/s", f / 1e12)  # noqa: E731
     fl = 2.0 * B * H * H
@@ -75,14 +79,15 @@ def main():
         ("fwd_fused2_D18_logp", lambda: call("harl_mlp_fwd_fused2", ptr(obs), 18, None, B, 18, ptr(W1), ptr(b), 1, ptr(W), ptr(b), H, 0, ptr(xh1), ptr(mask), ptr(rstd), ptr(mu0), ptr(rstd0), ptr(xh2), ptr(mask), ptr(rstd), None, s), GF(fl + 2.0 * B * 18 * H)),
         ("x0n_D18", lambda: call("harl_mlp_x0n_wide", ptr(obs), 18, None, B, 18, 1, ptr(x0n32), ptr(mu0), ptr(rstd0), s), GB(B * (72 + 128 + 8))),
         ("x0n_D54", lambda: call("harl_mlp_x0n_wide", ptr(sobs), 54, None, B, 54, 1, ptr(x0n64), ptr(mu0), ptr(rstd0), s), GB(B * (216 + 256 + 8))),
+        ("x0n_multi_mpe", lambda: _lib.x0n_multi(multi_problems, tag=None), GB(B * (3 * (72 + 128 + 8) + 216 + 256 + 8))),
         ("fwd_fused2x_train", lambda: call("harl_mlp_fwd_fused2x", ptr(x0n32), B, ptr(W1), 18, ptr(b), ptr(W), ptr(b), H, 1, ptr(xh1), ptr(mask), ptr(rstd), ptr(xh2), ptr(mask), ptr(rstd), s), GF(fl + 2.0 * B * 18 * H)),
         ("fwd_fused2x_logp", lambda: call("harl_mlp_fwd_fused2x", ptr(x0n32), B, ptr(W1), 18, ptr(b), ptr(W), ptr(b), H, 0, ptr(xh1), ptr(mask), ptr(rstd), ptr(xh2), ptr(mask), ptr(rstd), s), GF(fl + 2.0 * B * 18 * H)),
         ("fwd_wide_K64", lambda: call("harl_mlp_fwd_wide", ptr(x0n64), B, 64, ptr(W1c), 54, ptr(b), H, ptr(wimg), ptr(xh1), ptr(mask), ptr(rstd), s), GB(B * (256 + 512 + 20))),
         ("fwd_hidden", lambda: call("harl_mlp_fwd_hidden", ptr(xh1), B, H, H, ptr(W), ptr(b), ptr(xh2), ptr(mask), ptr(rstd), s), GF(fl)),
         ("bwd_dx", lambda: call("harl_mlp_bwd_dx", ptr(dz), ptr(xh1), ptr(mask), ptr(rstd), B, H, H, ptr(W), ptr(dz2), None, 0, None, 0, s), GF(fl)),
-        ("bwd_full_fill", lambda: call("harl_mlp_bwd_dx_dw", ptr(dz), ptr(xh1), ptr(mask), ptr(rstd), B, H, H, ptr(W), ptr(dz2), None, 0, None, ptr(part), n_wg, 1, s), GF(2 * fl)),
+        ("bwd_full_fill", lambda: call("harl_mlp_bwd_dx_dw", ptr(dz), ptr(xh1), ptr(mask), ptr(rstd), B, H, H, ptr(W), ptr(dz2), None, 0, None, ptr(part), n_wg, 2, s), GF(2 * fl)),
         ("bwd_full_nofill", lambda: call("harl_mlp_bwd_dx_dw", ptr(dz), ptr(xh1), ptr(mask), ptr(rstd), B, H, H, ptr(W), ptr(dz2), None, 0, None, ptr(part), n_wg, 0, s), GF(2 * fl)),
-        ("bwd_full_dw1_fill", lambda: call("harl_mlp_bwd_dx_dw", ptr(dz), ptr(xh1), ptr(mask), ptr(rstd), B, H, H, ptr(W), None, ptr(x0n32), 32, ptr(part_1), ptr(part), n_wg, 1, s), GF(2 * fl + 2.0 * B * H * 18)),
+        ("bwd_full_dw1_fill", lambda: call("harl_mlp_bwd_dx_dw", ptr(dz), ptr(xh1), ptr(mask), ptr(rstd), B, H, H, ptr(W), None, ptr(x0n32), 32, ptr(part_1), ptr(part), n_wg, 2, s), GF(2 * fl + 2.0 * B * H * 18)),
         ("bwd_full_dw1_nofill", lambda: call("harl_mlp_bwd_dx_dw", ptr(dz), ptr(xh1), ptr(mask), ptr(rstd), B, H, H, ptr(W), None, ptr(x0n32), 32, ptr(part_1), ptr(part), n_wg, 0, s), GF(2 * fl + 2.0 * B * H * 18)),
         ("bwd_dx_dw1_fused", lambda: call("harl_mlp_bwd_dx", ptr(dz), ptr(xh1), ptr(mask), ptr(rstd), B, H, H, ptr(W), None, ptr(x0n32), 32, ptr(part_1), n_wg, s), GF(fl + 2.0 * B * H * 18)),
         ("dw_hidden", lambda: call("harl_mlp_dw_partials", ptr(dz), 0, 0, H, ptr(xh1), 0, 0, None, None, None, H, B, ptr(part), n_wg, s), GF(fl)),
