@@ -118,6 +118,8 @@ SIGNATURES = {
                           _l, _l, _vp, _vp, _i, _vp],
     "harl_cat_head_logp": [_vp, _i, _vp, _i, _l, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _l, _l, _vp],
     "harl_cat_head_loss": [_vp, _i, _vp, _i, _l, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _d, _f, _i, _l, _l, _vp, _vp, _i, _vp],
+    "harl_cat_head_fvp": [_vp, _vp, _vp, _i, _vp, _i, _l, _vp, _l, _l, _vp],
+    "harl_cat_kl_sum": [_vp, _vp, _l, _i, _vp, _vp],
     "harl_trpo_begin": [_vp, _vp, _l, _i, _vp, _vp, _vp, _vp, _l, _vp, _vp, _vp, _vp],
     "harl_trpo_step": [_vp, _vp, _vp, _vp, _vp, _vp, _l, _f, _vp, _vp, _vp],
     "harl_trpo_ls_candidate": [_vp, _vp, _vp, _vp, _l, _vp],

@@ -14,6 +14,8 @@
 // absent from maximum, sum and entropy and their gradient is written as 0; an unavailable action's logit is the fp32 value
 // -1e10 (act.py / distributions.py:52-55, not -inf), set BEFORE the maximum; samples past M (and the padding sequences of a
 // recurrent batch) add nothing to part_scalars and their gradient rows are 0.
+// HATRPO (harl/algorithms/actors/hatrpo.py:77-177, harl/utils/trpo_util.py:47-51,132-158) adds the surrogate in its form (mode 1
+// of the loss), the head part of the Fisher-vector product (k_cat_head_fvp) and the KL sum over rows this wide (k_cat_kl).
 #include "common.h"
 #include "../../include/harl_hip.h"
 
@@ -132,7 +134,9 @@ __device__ __forceinline__ void group_emit(const float (&v)[64], float (&out)[64
   }
 }
 
-template <bool TRAIN, bool VEC>
+// TRPO (harl_cat_head_loss mode 1, hatrpo.py:77-90): the surrogate +imp * adv * factor * active itself, no clip and no entropy
+// term in the gradient.  A template parameter, so that the code of modes 0 / 2 is the code it was.
+template <bool TRAIN, bool VEC, bool TRPO = false>
 __global__ __launch_bounds__(WG_THREADS) void k_cat_head(CatArgs A) {
   __shared__ float red[WAVES_PER_WG * PS_STRIDE];
   const int lane = threadIdx.x & 63, wave = wave_id(), i = lane & 31, h = lane >> 5;
@@ -201,10 +205,15 @@ __global__ __launch_bounds__(WG_THREADS) void k_cat_head(CatArgs A) {
       const float inrange = (imp >= A.clip_lo && imp <= A.clip_hi) ? 1.f : 0.f;
       float gsel = surr1 < surr2 ? 1.f : (surr1 > surr2 ? inrange : 0.5f + 0.5f * inrange);  // torch.min ties split evenly
       if (A.mode != 0) gsel = 1.f;  // HAA2C: no clip (haa2c.py:70-80)
-      dlp = valid ? -fct * actv * advn * gsel * imp : 0.f;
-      ecoef = valid ? -A.entropy_coef * actv : 0.f;  // the entropy bonus is active-mask weighted (act.py:143-150)
+      if constexpr (TRPO) {
+        dlp = valid ? fct * actv * advn * imp : 0.f;
+      } else {
+        dlp = valid ? -fct * actv * advn * gsel * imp : 0.f;
+        ecoef = valid ? -A.entropy_coef * actv : 0.f;  // the entropy bonus is active-mask weighted (act.py:143-150)
+      }
       if (valid && h == 0) {
-        sc[0] += -fct * (A.mode == 2 ? surr1 : mn) * actv;
+        if constexpr (TRPO) sc[0] += surr1 * fct * actv;
+        else sc[0] += -fct * (A.mode == 2 ? surr1 : mn) * actv;
         sc[1] += actv;
         sc[2] += ent * actv;
         sc[3] += imp;
@@ -258,8 +267,163 @@ __global__ __launch_bounds__(WG_THREADS) void k_cat_head(CatArgs A) {
   }
 }
 
+// =============================================================================================
+// HATRPO Fisher-vector product, head part (harl/utils/trpo_util.py:132-158): the grouped counterpart of k_actor_head_fvp
+// (heads.hip), whose arithmetic this is.  z_dot = zd_a + zd_b is the tangent of the logits (two harl_mlp_linear products per
+// group), M = identity on the normalised logits q = z - logsumexp(z) over ALL n entries -- a masked entry's q = -1e10 - lse
+// still moves with lse -- and the log-softmax backward of dq = q_dot goes IN PLACE into the logits images:
+//   S = sum_un p_c z_dot_c,  q_dot_c = [un_c] z_dot_c - S,  sum_dq = sum_un z_dot_c - n S,
+//   out_c = un_c ? (z_dot_c - S) - p_c sum_dq : 0          (un_c: available and c < n)
+// pass 1 is online over the groups like group_stats: running maximum m, se = sum e^(z - m) and U = sum_un e^(z - m) z_dot,
+// rescaled together; S = U / se.  pass 2 reloads logits and tangents and writes.  group_load leaves exactly -1e10 in a masked
+// entry and PAD in a padding row, so un_c is `logit > -1e10`: no second walk over the availability row.
+// =============================================================================================
+struct CatFvpArgs {
+  float *z[MAXG];  // logits images, overwritten with the result
+  const float *zd_a[MAXG], *zd_b[MAXG];  // tangent images in the layout of z (zd_b: NULL = none)
+  int sp[MAXG];
+  int n_groups, n;
+  long M, m_valid, m_pad;
+  const float *avail;  // [M, n] by batch position; NULL = every action available
+  long n_slabs;
+};
+
+constexpr float MASKED = -1e10f;
+
+template <int SP>
+__device__ __forceinline__ void tangent_load(const float *a, const float *b, long slab, int lane, float (&d)[64]) {
+  float t[SP / 2];
+  atl_load<SP>(a, slab, lane, t);
+  if (b) {  // wave-uniform
+    float u[SP / 2];
+    atl_load<SP>(b, slab, lane, u);
+#pragma unroll
+    for (int R = 0; R < SP / 2; ++R) t[R] += u[R];
+  }
+#pragma unroll
+  for (int R = 0; R < SP / 2; ++R) d[R] = t[R];
+}
+
+// pass 1 over one group: m is the same in both lanes of a sample; se, U and sz are per-lane partial sums
+template <int SP>
+__device__ __forceinline__ void fvp_stats(const float (&v)[64], const float (&d)[64], float &m, float &se, float &U, float &sz) {
+  float gm = PAD;
+#pragma unroll
+  for (int R = 0; R < SP / 2; ++R) gm = fmaxf(gm, v[R]);
+  gm = fmaxf(gm, wave_xor32(gm));
+  const float mn = fmaxf(m, gm);
+  const float c = expf(m - mn);  // first group: 0, and se = U = 0
+  se *= c;
+  U *= c;
+  m = mn;
+#pragma unroll
+  for (int R = 0; R < SP / 2; ++R) {
+    const float e = expf(v[R] - mn);
+    se += e;
+    const bool un = v[R] > MASKED;  // (selects, not products: the tangent of a padding row is whatever the GEMM left there)
+    U += un ? e * d[R] : 0.f;
+    sz += un ? d[R] : 0.f;
+  }
+}
+
+// pass 2 over one group: the result takes the tangent's place in d
+template <int SP>
+__device__ __forceinline__ void fvp_emit(const float (&v)[64], float (&d)[64], bool valid, float lse, float S, float sum_dq) {
+#pragma unroll
+  for (int R = 0; R < SP / 2; ++R) {
+    const float z = valid ? v[R] : MASKED;  // (an invalid sample as a row of masked entries: one select, no branch per entry)
+    const float p = expf(z - lse);
+    d[R] = z > MASKED ? (d[R] - S) - p * sum_dq : 0.f;
+  }
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(WG_THREADS, 2) void k_cat_head_fvp(CatFvpArgs A) {
+  const int lane = threadIdx.x & 63, wave = wave_id(), i = lane & 31, h = lane >> 5;
+  for (long slab = (long)blockIdx.x * WAVES_PER_WG + wave; slab < A.n_slabs; slab += (long)gridDim.x * WAVES_PER_WG) {
+    const long j = slab * SLAB + i;
+    const bool valid = j < A.M && (A.m_pad == 0 || (j % A.m_pad) < A.m_valid);
+    const long jc = j < A.M ? j : A.M - 1;
+    const float *av_row = A.avail ? A.avail + jc * (long)A.n : nullptr;
+
+    float v[64], d[64];
+    float m = PAD, se = 0.f, U = 0.f, sz = 0.f;
+    for (int g = 0; g < A.n_groups; ++g) {
+      const int cnt = min(GROUP, A.n - GROUP * g);
+      const float *av = av_row ? av_row + GROUP * g : nullptr;
+      if (A.sp[g] == 128) {
+        group_load<128, VEC>(A.z[g], slab, lane, h, cnt, av, v);
+        tangent_load<128>(A.zd_a[g], A.zd_b[g], slab, lane, d);
+        fvp_stats<128>(v, d, m, se, U, sz);
+      } else {
+        group_load<64, VEC>(A.z[g], slab, lane, h, cnt, av, v);
+        tangent_load<64>(A.zd_a[g], A.zd_b[g], slab, lane, d);
+        fvp_stats<64>(v, d, m, se, U, sz);
+      }
+    }
+    se = wave_sum32(se);
+    U = wave_sum32(U);
+    sz = wave_sum32(sz);
+    const float lse = m + logf(se);
+    const float S = U / se;
+    const float sum_dq = sz - (float)A.n * S;  // sum over ALL n entries of q_dot_c = [un_c] z_dot_c - S
+
+    for (int g = 0; g < A.n_groups; ++g) {
+      const int cnt = min(GROUP, A.n - GROUP * g);
+      const float *av = av_row ? av_row + GROUP * g : nullptr;
+      if (A.sp[g] == 128) {
+        group_load<128, VEC>(A.z[g], slab, lane, h, cnt, av, v);
+        tangent_load<128>(A.zd_a[g], A.zd_b[g], slab, lane, d);
+        fvp_emit<128>(v, d, valid, lse, S, sum_dq);
+        atl_store<128>(A.z[g], slab, lane, d);
+      } else {
+        group_load<64, VEC>(A.z[g], slab, lane, h, cnt, av, v);
+        tangent_load<64>(A.zd_a[g], A.zd_b[g], slab, lane, d);
+        fvp_emit<64>(v, d, valid, lse, S, sum_dq);
+        float t[32];
+#pragma unroll
+        for (int R = 0; R < 32; ++R) t[R] = d[R];
+        atl_store<64>(A.z[g], slab, lane, t);
+      }
+    }
+  }
+}
+
+// sum over rows of kl_approx(old || new) on normalised logits (trpo_util.py:47-51), rows of 65..512 entries: one wave per row,
+// the lanes walk it (k_trpo_kl, heads.hip: one THREAD per row).  The reference's fp32 term order per entry -- with it a masked
+// entry (both values exactly -1e10) contributes exactly 0 -- lane-partial fp32 sums, one wave reduction per row, fp64 across rows.
+template <bool VEC>
+__global__ __launch_bounds__(WG_THREADS) void k_cat_kl(const float *__restrict__ ho, const float *__restrict__ hn, long M, int n,
+                                                       double *__restrict__ out) {
+  __shared__ double sh[WAVES_PER_WG];
+  const int lane = threadIdx.x & 63, wave = wave_id();
+  double acc = 0;
+  for (long r = (long)blockIdx.x * WAVES_PER_WG + wave; r < M; r += (long)gridDim.x * WAVES_PER_WG) {
+    float k = 0.f;
+    if constexpr (VEC) {  // n a multiple of 4, 16-byte aligned rows
+      const f32x4 *po = reinterpret_cast<const f32x4 *>(ho + r * (long)n), *pn = reinterpret_cast<const f32x4 *>(hn + r * (long)n);
+      for (int c = lane; c < n / 4; c += WAVE) {
+        const f32x4 pp = po[c], q = pn[c];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) k += (expf(q[e] - pp[e]) - 1.f - q[e]) + pp[e];
+      }
+    } else {
+      const float *po = ho + r * (long)n, *pn = hn + r * (long)n;
+      for (int c = lane; c < n; c += WAVE) {
+        const float pp = po[c], q = pn[c];
+        k += (expf(q - pp) - 1.f - q) + pp;
+      }
+    }
+    acc += (double)wave_reduce_sum(k);  // (the same value in every lane)
+  }
+  if (lane == 0) sh[wave] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) atomicAdd(out, (sh[0] + sh[1]) + (sh[2] + sh[3]));
+}
+
 // groups of a Discrete(n) head: rows [128 g, min(128 (g + 1), n)), full groups ATL(128), the last one ATL(64 | 128)
-int fill_layout(CatArgs &A, float *const *z, int n_groups, const int *sp, int n) {
+template <class Args>
+int fill_layout(Args &A, float *const *z, int n_groups, const int *sp, int n) {
   if (n < 1 || n > GROUP * MAXG || n_groups != (n + GROUP - 1) / GROUP || !z || !sp)
     return bad("Categorical head: 1..512 actions in ceil(n / 128) groups");
   for (int g = 0; g < n_groups; ++g) {
@@ -275,8 +439,39 @@ int fill_layout(CatArgs &A, float *const *z, int n_groups, const int *sp, int n)
 }
 
 // 16-byte mask loads: every availability row starts on a 16-byte boundary and every group holds a multiple of 4 actions
-bool vec_mask(const CatArgs &A) { return A.avail && (A.n & 3) == 0 && (reinterpret_cast<uintptr_t>(A.avail) & 15) == 0; }
+template <class Args>
+bool vec_mask(const Args &A) { return A.avail && (A.n & 3) == 0 && (reinterpret_cast<uintptr_t>(A.avail) & 15) == 0; }
 }  // namespace
+
+extern "C" int harl_cat_head_fvp(float *const *z, const float *const *zd_a, const float *const *zd_b, int n_groups,
+                                 const int *sp, int n, long M, const float *avail, long m_valid, long m_pad, void *stream) {
+  if (M <= 0) return 0;
+  CatFvpArgs A{};
+  if (int rc = fill_layout(A, z, n_groups, sp, n)) return rc;
+  if (!zd_a) return bad("harl_cat_head_fvp: the tangent images zd_a are required");
+  for (int g = 0; g < n_groups; ++g) {
+    if (!zd_a[g] || (zd_b && !zd_b[g])) return bad("harl_cat_head_fvp: one tangent image per group");
+    A.zd_a[g] = zd_a[g];
+    A.zd_b[g] = zd_b ? zd_b[g] : nullptr;
+  }
+  A.M = M; A.m_valid = m_valid; A.m_pad = m_pad; A.avail = avail;
+  A.n_slabs = n_slabs_of(M);
+  const int grid = persistent_grid(A.n_slabs, 4);
+  if (vec_mask(A)) hipLaunchKernelGGL((k_cat_head_fvp<true>), dim3(grid), dim3(WG_THREADS), 0, (hipStream_t)stream, A);
+  else hipLaunchKernelGGL((k_cat_head_fvp<false>), dim3(grid), dim3(WG_THREADS), 0, (hipStream_t)stream, A);
+  return check_launch("harl_cat_head_fvp");
+}
+
+extern "C" int harl_cat_kl_sum(const float *head_old, const float *head_new, long M, int n, double *out_sum, void *stream) {
+  if (M <= 0) return 0;
+  if (!head_old || !head_new || !out_sum || n < 1) return bad("harl_cat_kl_sum: head_old, head_new, out_sum and n >= 1 are required");
+  const long wgs = (M + WAVES_PER_WG - 1) / WAVES_PER_WG;
+  const int grid = (int)(wgs < 2048 ? wgs : 2048);  // up to eight workgroups per CU: nothing but loads in flight
+  const bool vec = (n & 3) == 0 && ((reinterpret_cast<uintptr_t>(head_old) | reinterpret_cast<uintptr_t>(head_new)) & 15) == 0;
+  if (vec) hipLaunchKernelGGL((k_cat_kl<true>), dim3(grid), dim3(WG_THREADS), 0, (hipStream_t)stream, head_old, head_new, M, n, out_sum);
+  else hipLaunchKernelGGL((k_cat_kl<false>), dim3(grid), dim3(WG_THREADS), 0, (hipStream_t)stream, head_old, head_new, M, n, out_sum);
+  return check_launch("harl_cat_kl_sum");
+}
 
 extern "C" int harl_cat_head_logp(const float *const *z, int n_groups, const int *sp, int n, long M, const int64_t *idx,
                                   const float *actions, const float *avail, float *logp_out, float *ent_out,
@@ -304,7 +499,7 @@ extern "C" int harl_cat_head_loss(float *const *z, int n_groups, const int *sp, 
   if (M <= 0) return 0;
   CatArgs A{};
   if (int rc = fill_layout(A, z, n_groups, sp, n)) return rc;
-  if (mode != 0 && mode != 2) return bad("harl_cat_head_loss: mode 0 (HAPPO / MAPPO) or 2 (HAA2C)");
+  if (mode < 0 || mode > 2) return bad("harl_cat_head_loss: mode 0 (HAPPO / MAPPO), 1 (HATRPO) or 2 (HAA2C)");
   if (n_blocks < 1) return bad("harl_cat_head_loss: n_blocks must be positive");
   if (!actions || !old_logp || !adv || !part_scalars) return bad("harl_cat_head_loss: actions, old_logp, adv and part_scalars are required");
   A.M = M; A.m_valid = m_valid; A.m_pad = m_pad; A.idx = idx;
@@ -314,7 +509,11 @@ extern "C" int harl_cat_head_loss(float *const *z, int n_groups, const int *sp, 
   A.entropy_coef = entropy_coef; A.mode = mode;
   A.logp_out = logp_out; A.part_scalars = part_scalars;
   A.n_slabs = n_slabs_of(M);
-  if (vec_mask(A)) hipLaunchKernelGGL((k_cat_head<true, true>), dim3(n_blocks), dim3(WG_THREADS), 0, (hipStream_t)stream, A);
-  else hipLaunchKernelGGL((k_cat_head<true, false>), dim3(n_blocks), dim3(WG_THREADS), 0, (hipStream_t)stream, A);
+  const dim3 grid(n_blocks), wg(WG_THREADS);
+  if (mode == 1) {
+    if (vec_mask(A)) hipLaunchKernelGGL((k_cat_head<true, true, true>), grid, wg, 0, (hipStream_t)stream, A);
+    else hipLaunchKernelGGL((k_cat_head<true, false, true>), grid, wg, 0, (hipStream_t)stream, A);
+  } else if (vec_mask(A)) hipLaunchKernelGGL((k_cat_head<true, true>), grid, wg, 0, (hipStream_t)stream, A);
+  else hipLaunchKernelGGL((k_cat_head<true, false>), grid, wg, 0, (hipStream_t)stream, A);
   return check_launch("harl_cat_head_loss");
 }

@@ -169,13 +169,15 @@ class OnPolicyBase:
         M = obs.shape[0]
         net = self.actor
         out = torch.empty(M, net.act_w, **self.tpdv)
-        head = torch.empty(M, net.act_dim, **self.tpdv)
+        # zeros, not empty: the distribution object built below validates its parameters, so where the launches are recorded
+        # instead of executed (the host-side tests) it must not be handed whatever the allocator's recycled block held
+        head = torch.zeros(M, net.act_dim, **self.tpdv)
         net.fold()
         self._logp_pass(obs, action, avail, M, out, head_out=head, rnn_states=rnn_states_actor, masks=masks)
         # entropy rows, their (active-mask-weighted) mean and sigma behind the C ABI (harl_dist_rows / harl_masked_moments /
         # harl_moments_mean); the distribution OBJECT the reference returns is built from the kernel outputs
         ent_rows = torch.empty(M, **self.tpdv)
-        sigma = None if net.discrete else torch.empty(net.act_dim, **self.tpdv)
+        sigma = None if net.discrete else torch.ones(net.act_dim, **self.tpdv)  # (a valid scale for the same reason)
         self._dist_rows(head, M, ent_rows=ent_rows, sigma_out=sigma)
         am = None
         if not net.md and active_masks is not None and self.use_policy_active_masks:  # (act.py:117-141: never for MultiDiscrete)

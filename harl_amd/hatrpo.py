@@ -18,6 +18,7 @@ import torch
 from . import _lib
 from ._lib import call, ptr, stream
 from .buffers import OnPolicyActorBuffer, consume_randperm, rng_sync
+from .configs import CAT_WIDE_REFUSALS, trpo_cat_wide_enabled
 from .happo import OnPolicyBase
 from .nets import build_seq, consume_policy_init_rng, seq_compact
 from .valuenorm import _as_dev
@@ -27,10 +28,11 @@ class HATRPO(OnPolicyBase):
     def __init__(self, args, obs_space, act_space, device=torch.device("cuda:0")):
         assert act_space.__class__.__name__ != "MultiDiscrete", \
             "only continuous and discrete action space is supported by HATRPO."
-        if act_space.__class__.__name__ == "Discrete" and int(act_space.n) > 64:
-            from .nets import CAT_WIDE_REFUSALS
+        if act_space.__class__.__name__ == "Discrete" and int(act_space.n) > 64 and not trpo_cat_wide_enabled():
             raise NotImplementedError(CAT_WIDE_REFUSALS["hatrpo"] if int(act_space.n) <= 512 else CAT_WIDE_REFUSALS["n"])
-        super().__init__(args, obs_space, act_space, device)
+        super().__init__(args, obs_space, act_space, device)  # (HARL_TRPO_CAT_WIDE=1: n > 512, 256-wide and non-ReLU are refused there)
+        if self.actor.cat_wide and self.actor.recurrent and self.actor.gru_wide:
+            raise NotImplementedError(CAT_WIDE_REFUSALS["hatrpo_gru_wide"])
         self.kl_threshold = args["kl_threshold"]
         self.ls_step = args["ls_step"]
         self.accept_ratio = args["accept_ratio"]
@@ -57,10 +59,16 @@ class HATRPO(OnPolicyBase):
         s = stream()
         fx, fmask, frstd, fh = net.feat()
         mv, mp = (seq["m"], seq["m_pad"]) if seq is not None else (0, 0)
-        call("harl_actor_head_loss", ptr(fx), ptr(fmask), ptr(frstd), m, fh,
-             ptr(Wp), ptr(bp), ptr(net.log_std()), net.std_x_coef, net.std_y_coef, int(net.discrete), net.act_dim,
-             ptr(idx), ptr(actions), ptr(avail), ptr(old_logp), ptr(adv), ptr(adv_moments), ptr(factor), ptr(active),
-             0.0, 0.0, int(self.action_aggregation == "mean"), 1, mv, mp, None, ptr(net.dz[0]), ptr(net.dhead), ptr(net.part_scalars), None, 0, s)
+        if net.cat_wide:  # Categorical of 65..512 actions (csrc/cathead.hip): logits of every group, the loss in HATRPO's form (mode 1)
+            net.md_logits(m)
+            call("harl_cat_head_loss", *net.cat_layout(), m, ptr(idx), ptr(actions), ptr(avail), ptr(old_logp), ptr(adv),
+                 ptr(adv_moments), ptr(factor), ptr(active), 0.0, 0.0, 1, mv, mp, None, ptr(net.part_scalars),
+                 _lib.load().harl_head_blocks(m), s, tag="cat_head_loss")
+        else:
+            call("harl_actor_head_loss", ptr(fx), ptr(fmask), ptr(frstd), m, fh,
+                 ptr(Wp), ptr(bp), ptr(net.log_std()), net.std_x_coef, net.std_y_coef, int(net.discrete), net.act_dim,
+                 ptr(idx), ptr(actions), ptr(avail), ptr(old_logp), ptr(adv), ptr(adv_moments), ptr(factor), ptr(active),
+                 0.0, 0.0, int(self.action_aggregation == "mean"), 1, mv, mp, None, ptr(net.dz[0]), ptr(net.dhead), ptr(net.part_scalars), None, 0, s)
         call("harl_reduce_scalars_set", ptr(net.part_scalars), _lib.load().harl_head_blocks(m), ptr(net.scalars), s)
         grad = None
         if want_grad:
@@ -92,7 +100,8 @@ class HATRPO(OnPolicyBase):
         if self._tangent_ws is None or self._tangent_ws["rows"] < m:
             mp = ((m + 31) // 32) * 32
             self._tangent_ws = dict(rows=m, xd=[torch.empty(mp * h, **self.tpdv) for h in hs],
-                                    pack_d=torch.empty_like(net.pack_arena))
+                                    # (zeros: a group's tangent pack keeps the zero rows past its last action, like the pack)
+                                    pack_d=torch.zeros_like(net.pack_arena) if net.grouped else torch.empty_like(net.pack_arena))
             if net.recurrent:
                 H = hs[-1]
                 self._tangent_ws["gates"] = [torch.empty(mp * H, **self.tpdv) for _ in range(4)]  # g_r, g_z, g_nx, g_nh
@@ -183,11 +192,14 @@ class HATRPO(OnPolicyBase):
                  ptr(net.rnn_rstd), H, seq["L"], seq["m_pad"], ptr(ws["ydot"]), s, tag="gru_tangent")
             xLdot = ws["ydot"]
             mv, mp_ = seq["m"], seq["m_pad"]
-        Whp, bhp = net._packs[-1]
-        Whpd, bhpd = packs_d[-1]
-        call("harl_actor_head_fvp", ptr(fx), ptr(xLdot), ptr(fmask), ptr(frstd), m, fh,
-             ptr(Whp), ptr(bhp), ptr(Whpd), ptr(bhpd), ptr(net.log_std()), net.std_x_coef, net.std_y_coef,
-             int(net.discrete), net.act_dim, ptr(avail), mv, mp_, ptr(net.dz[0]), ptr(net.dhead), s)
+        if net.cat_wide:
+            self._cat_head_fvp(m, fx, fh, xLdot, pd, avail, mv, mp_)
+        else:
+            Whp, bhp = net._packs[-1]
+            Whpd, bhpd = packs_d[-1]
+            call("harl_actor_head_fvp", ptr(fx), ptr(xLdot), ptr(fmask), ptr(frstd), m, fh,
+                 ptr(Whp), ptr(bhp), ptr(Whpd), ptr(bhpd), ptr(net.log_std()), net.std_x_coef, net.std_y_coef,
+                 int(net.discrete), net.act_dim, ptr(avail), mv, mp_, ptr(net.dz[0]), ptr(net.dhead), s)
         net.backward_trunk(obs, idx, m, seq=seq)
         net.unfold_grads()
         g = net.flat_grad
@@ -206,6 +218,28 @@ class HATRPO(OnPolicyBase):
              int(ls_off), net.act_dim, net.std_x_coef, net.std_y_coef, s)
         return out
 
+    def _cat_head_fvp(self, m, fx, fh, xLdot, pack_d, avail, m_valid, m_pad) -> None:
+        """Head part of F v for a Categorical head of 65..512 actions (csrc/cathead.hip): the logits again (the loss or the
+        previous product overwrote the images), per group the two halves of their tangent W'_g x_dot_L and W'_g_dot x_hat_L +
+        b'_g_dot as raw GEMMs, then harl_cat_head_fvp, which leaves the log-softmax backward of q_dot in the logits images --
+        where backward_trunk (md_backward) reads d(loss)/d(logits) after a loss launch.  The groups are layer-table entries:
+        ``pack_d`` holds their W'_g_dot / b'_g_dot at the offsets of the folded packs (harl_fold_tangent_table)."""
+        import ctypes as C
+        net, ws, s = self.actor, self._tangent_ws, stream()
+        rows = ws["xd"][0].numel() // net.hidden_sizes[0]
+        if ws.get("cat_zd") is None:
+            ws["cat_zd"] = [[torch.empty(rows * sp, **self.tpdv) for sp in net._md_sp] for _ in range(2)]
+            ws["cat_zero_bias"] = torch.zeros(128, **self.tpdv)
+        net.md_logits(m)
+        G = len(net._md_sp)
+        for (Wp, _), (pw, pb, _, k), za, zb, sp in zip(net._head_packs, net._pack_slots[-G:], *ws["cat_zd"], net._md_sp):
+            call("harl_mlp_linear", ptr(xLdot), m, fh, sp, ptr(Wp), ptr(ws["cat_zero_bias"]), ptr(za), s, tag="md_linear")
+            call("harl_mlp_linear", ptr(fx), m, fh, sp, ptr(pack_d[pw:pw + sp * k]), ptr(pack_d[pb:pb + sp]), ptr(zb), s,
+                 tag="md_linear")
+        zs, _, sps, n = net.cat_layout()
+        za, zb = [(C.c_void_p * G)(*[t.data_ptr() for t in imgs]) for imgs in ws["cat_zd"]]
+        call("harl_cat_head_fvp", zs, za, zb, G, sps, n, m, ptr(avail), m_valid, m_pad, s, tag="cat_head_fvp")
+
     def _head_outputs(self, obs, m, actions, avail, reuse_trunk=False, seq=None, avail_rows=None) -> torch.Tensor:
         """Distribution parameters at the current weights: Gaussian mean / normalised logits, [rows, act_dim].
         ``reuse_trunk``: a _surrogate() call under the same weights has just left x_hat_L in the workspace.
@@ -219,9 +253,14 @@ class HATRPO(OnPolicyBase):
         fx, _, _, fh = net.feat()
         Wp, bp = net._packs[-1]
         ho = torch.empty(m, net.act_dim, **self.tpdv)
-        call("harl_actor_head_logp", ptr(fx), m, fh, ptr(Wp), ptr(bp), ptr(net.log_std()), net.std_x_coef, net.std_y_coef,
-             int(net.discrete), net.act_dim, None, ptr(avail_rows), None, None, None, 0, ptr(ho), seq["m"], seq["m_pad"],
-             stream(), tag="actor_head_logp")
+        if net.cat_wide:
+            net.md_logits(m)
+            call("harl_cat_head_logp", *net.cat_layout(), m, None, None, ptr(avail_rows), None, None, None, None, ptr(ho),
+                 seq["m"], seq["m_pad"], stream(), tag="cat_head_logp")
+        else:
+            call("harl_actor_head_logp", ptr(fx), m, fh, ptr(Wp), ptr(bp), ptr(net.log_std()), net.std_x_coef, net.std_y_coef,
+                 int(net.discrete), net.act_dim, None, ptr(avail_rows), None, None, None, 0, ptr(ho), seq["m"], seq["m_pad"],
+                 stream(), tag="actor_head_logp")
         return seq_compact(ho, seq) if seq["m_pad"] != seq["m"] else ho
 
     def _kl_sum(self, head_old, ls_old, head_new, m, acc: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -230,8 +269,11 @@ class HATRPO(OnPolicyBase):
         net = self.actor
         if acc is None:
             acc = torch.zeros(1, dtype=torch.float64, device=self.device)
-        call("harl_trpo_kl_sum", ptr(head_old), ptr(head_new), ptr(ls_old), ptr(net.log_std()), net.std_x_coef,
-             net.std_y_coef, m, net.act_dim, int(net.discrete), ptr(acc), stream())
+        if net.cat_wide:  # rows of 65..512 entries: one wave per row (csrc/cathead.hip)
+            call("harl_cat_kl_sum", ptr(head_old), ptr(head_new), m, net.act_dim, ptr(acc), stream(), tag="cat_kl_sum")
+        else:
+            call("harl_trpo_kl_sum", ptr(head_old), ptr(head_new), ptr(ls_old), ptr(net.log_std()), net.std_x_coef,
+                 net.std_y_coef, m, net.act_dim, int(net.discrete), ptr(acc), stream())
         if self.comm.enabled:
             self.comm.all_reduce_sum(acc)
         return acc

@@ -116,6 +116,18 @@ def _cat_head_loss(a: Sequence) -> float:
     return M * row
 
 
+def _cat_head_fvp(a: Sequence) -> float:
+    # (z, zd_a, zd_b, n_groups, sp, n, M, avail, m_valid, m_pad, stream): the logits images, every tangent set and the availability
+    # row are read in both passes (nothing of a row is kept between them), the result overwrites the logits images
+    G, n, M = a[3], a[5], a[6]
+    img = 4.0 * sum(a[4][g] for g in range(G))
+    return M * (2 * img * (1 + _nonnull((a[1], a[2]))) + (2 * 4.0 * n if a[7] else 0.0) + img)
+
+
+def _cat_kl_sum(a: Sequence) -> float:  # (head_old, head_new, M, n, out_sum, stream): both [M, n] arrays once
+    return a[2] * 2 * 4.0 * a[3]
+
+
 def _nonnull(arr) -> int:
     return sum(1 for p in arr if p)
 
@@ -265,6 +277,8 @@ ALGORITHMIC_BYTES: Dict[str, Callable[[Sequence], float]] = {
     "harl_mlp_panel_bwd": _panel_bwd,
     "harl_cat_head_logp": _cat_head_logp,
     "harl_cat_head_loss": _cat_head_loss,
+    "harl_cat_head_fvp": _cat_head_fvp,
+    "harl_cat_kl_sum": _cat_kl_sum,
     "harl_mlp_tangent_hidden": _tangent_hidden,
     "harl_mlp_tangent_hidden2": _tangent_hidden,  # (same leading arguments: xin_dot, xin, M, HI, HO)
 }

@@ -562,7 +562,23 @@ int harl_md_head_loss(const float *const *z, float *const *dz, int n_groups, con
  *   bonus -- aggregation, active masks and entropy normalisation exactly those of the Discrete branch of
  *   harl_actor_head_loss -- and d(unscaled loss)/d(logits) written IN PLACE into the images (0 in rows >= n and for samples
  *   past M / padding sequences).  part_scalars[n_blocks][HARL_PS_STRIDE] as harl_actor_head_loss
- *   ({0: sum loss*active, 1: sum active, 2: sum ent*active, 3: sum ratio, 4: count}); launched with n_blocks workgroups. */
+ *   ({0: sum loss*active, 1: sum active, 2: sum ent*active, 3: sum ratio, 4: count}); launched with n_blocks workgroups.
+ *   mode 1 = HATRPO's surrogate (harl/algorithms/actors/hatrpo.py:77-90), as `trpo == 1` of harl_actor_head_loss: scalar 0 is
+ *   sum +ratio*adv*factor*active, the gradient is that sum's (no clip, no entropy term; the entropy sum is still reported).
+ * harl_cat_head_fvp (harl/utils/trpo_util.py:132-158 with kl_approx, trpo_util.py:47-51,83-86; hatrpo.py:97-122): the head part
+ *   of the Fisher-vector product F v = J^T M (J v), the grouped counterpart of harl_actor_head_fvp's Discrete branch.  z: the
+ *   logits images; zd_a, zd_b (zd_b nullable): HOST arrays of n_groups device pointers to tangent images in the same layout,
+ *   z_dot = zd_a + zd_b (W' x_dot and W'_dot x_hat + b'_dot from harl_mlp_linear).  M = identity on the normalised logits over
+ *   ALL n entries, masked ones included; the log-softmax backward of q_dot is written IN PLACE into the images z (0 for
+ *   unavailable actions, rows >= n, samples past M and padding sequences), for harl_mlp_dw_partials / harl_mlp_bwd_dx as after
+ *   harl_cat_head_loss.  avail [M, n] is indexed BY BATCH POSITION (as in harl_actor_head_fvp); NOT yet divided by the batch
+ *   size (harl_trpo_fvp_finish).
+ * harl_cat_kl_sum (trpo_util.py:47-51,65-92; hatrpo.py:167-177): out_sum (double, accumulated) += sum over rows of
+ *   kl_approx(old || new) on row-major [M, n] normalised logits (head_out of harl_cat_head_logp) -- the Discrete branch of
+ *   harl_trpo_kl_sum with one wave per row instead of one thread. */
+int harl_cat_head_fvp(float *const *z, const float *const *zd_a, const float *const *zd_b, int n_groups, const int *sp, int n,
+                      long M, const float *avail, long m_valid, long m_pad, void *stream);
+int harl_cat_kl_sum(const float *head_old, const float *head_new, long M, int n, double *out_sum, void *stream);
 int harl_cat_head_logp(const float *const *z, int n_groups, const int *sp, int n, long M, const int64_t *idx,
                        const float *actions, const float *avail, float *logp_out, float *ent_out, const float *old_logp,
                        float *factor, float *head_out, long m_valid, long m_pad, void *stream);
