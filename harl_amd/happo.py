@@ -8,7 +8,6 @@ of the accumulated training statistics at the end.
 """
 from __future__ import annotations
 
-import os
 from typing import Optional
 
 import numpy as np
@@ -18,7 +17,7 @@ from . import _lib, graphs
 from ._lib import PS_STRIDE, call, ptr, stream
 from .buffers import OnPolicyActorBuffer, consume_randperm, minibatch_indices, rng_sync
 from .dist import Comm, local_minibatch_rows
-from .nets import FusedAdam, StochasticPolicy, build_seq, seq_compact
+from .nets import FusedAdam, StochasticPolicy, build_seq, routing_switches, seq_compact
 from .valuenorm import _as_dev
 
 
@@ -430,10 +429,9 @@ class HAPPO(OnPolicyBase):
     def _graph_consts(self) -> tuple:
         """Host scalars and routing switches that are baked into the launches of an optimiser step."""
         g = self.actor_optimizer.param_groups[0]
-        e = os.environ.get
         return (float(self.clip_param), float(self.entropy_coef), self.action_aggregation, self._surrogate_mode,
                 bool(self.use_max_grad_norm), float(self.max_grad_norm), tuple(g["betas"]), float(g["eps"]),
-                float(g["weight_decay"]), e("HARL_FUSED_UPDATE"), e("HARL_BWD_FUSED"), e("HARL_BWD_K64"), e("HARL_TRUNK_FUSED"))
+                float(g["weight_decay"])) + routing_switches()
 
     def update(self, sample):
         """API-compatible single update on an already-gathered minibatch (tuple order of happo.py:37-48).

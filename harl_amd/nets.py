@@ -14,7 +14,7 @@ from __future__ import annotations
 
 import math
 import os
-from typing import Dict, List, Optional, Sequence, Tuple
+from typing import Dict, List, NamedTuple, Optional, Sequence, Tuple
 
 import torch
 import torch.nn as nn
@@ -59,6 +59,19 @@ def _bwd_fused_mode(M: int = 0) -> str:
     if m == "auto":
         return "1" if M >= BWD_FUSED_MIN_ROWS else "0"
     return m
+
+
+# switches baked into the launches of an optimiser step: their values are part of every captured step's key (HARL_GRAPH=1)
+ROUTING_SWITCHES = ("HARL_FUSED_UPDATE", "HARL_BWD_FUSED", "HARL_BWD_K64", "HARL_TRUNK_FUSED")
+# _FlatNet._first_launch.  image: "cached" = the launch reads the image of X[idx] in self.x0n (_x0n_image); "cached_identity" =
+# the same, taken with idx None only; "clobbers" = it reads X itself and may write self.x0n, so the cache key is dropped
+_Route = NamedTuple("_Route", [("kind", str), ("image", str)])
+_ROUTES = {k: _Route(k, im) for k, im in dict(act="cached", panel="cached", trunk="cached", fused2x="cached_identity",
+                                              fused2="clobbers", wide="cached", input="clobbers").items()}
+
+
+def routing_switches() -> tuple:
+    return tuple(map(os.environ.get, ROUTING_SWITCHES))
 
 
 def prepare_x0n_multi(items) -> int:
@@ -316,8 +329,6 @@ class _FlatNet(nn.Module):
                 base = self._gru_pack_base + (2 * layer + mat) * (3 * H * H + 3 * H)
                 pw, pb = base + gate * H * H, base + 3 * H * H + gate * H
             else:
-                if self.recurrent and ei == L:
-                    pass
                 # head group: the GEMM kernels read a full [sp][k] matrix (zero rows past the last head / action)
                 orows = self._md_sp[ei - (len(ents) - len(self._md_sp))] if (self.grouped and ei >= len(ents) - len(self._md_sp)) else o
                 pw, pb = pack_off, pack_off + orows * k
@@ -404,8 +415,6 @@ class _FlatNet(nn.Module):
         self.rstd0 = torch.empty(mp, dtype=f32, device=dev)
         # narrow inputs: the forward pass leaves the normalised inputs behind as an ATL image for the dW_1 kernel
         self.kp0 = ((self.in_dim + 31) // 32) * 32
-        # inputs wider than 32 (csrc/wide.hip): x0n is the operand of the first-layer GEMM itself
-        self.wide = 32 < self.in_dim <= 512
         self._x0n_key = None
         self.x0n = torch.empty(mp * self.kp0, dtype=f32, device=dev) if (self.in_dim <= 64 or self.wide) else None
         self.w1img = (torch.empty(3 * self.hidden_sizes[0] * self.kp0 // 2, dtype=f32, device=dev)
@@ -531,36 +540,40 @@ class _FlatNet(nn.Module):
                  ptr(self.x0n), ptr(self.mu0), ptr(self.rstd0), s, tag="x0n_wide")
             self._x0n_key, self._x0n_src = key, (X, idx)
 
-    def prepare_x0n(self, X: torch.Tensor, idx: Optional[torch.Tensor], M: int) -> None:
-        """HARL_GRAPH=1, in front of a captured optimiser step (graphs.py): build the normalised-input image NOW if this
-        network's step reads one, so that the step itself finds it cached -- the image launch depends on a host-side cache
-        (first step of an update: miss, later ones: hit) and a replayed graph repeats what was captured.  Same launch, same
-        place in the stream as the eager step's.  Mirrors the routes of fused_args / forward_trunk; a route this gets wrong
-        fails the capture (_x0n_image), it never replays a stale image."""
+    def _first_launch(self, idx_is_none: bool, partial: bool) -> _Route:
+        """The launch a trunk forward starts with and what it does with self.x0n: forward_trunk dispatches on this, x0n_multi_item
+        and fused_last_ok ask it.  ``partial``: forward_trunk(upto=...), which has no whole-trunk launch.  The image does not
+        depend on it ("trunk" implies wide inputs, whose other routes read the same image of X[idx]; "fused2x": identity rows
+        only), so prepare_x0n in front of a captured step need not know.  Host path of every forward: comparisons only."""
         hs = self.hidden_sizes
-        self._ensure_ws(M)
         two_equal = len(hs) >= 2 and hs[0] == hs[1]
-        if self.act_id or self.panel or self.trunk_fused():
-            self._x0n_image(X, M, stream(), idx)
-        elif two_equal and self.in_dim <= 64 and idx is None:
-            self._x0n_image(X, M, stream())
-        elif two_equal and self.in_dim <= 32:
-            self._x0n_key = None  # harl_mlp_fwd_fused2 writes the gathered minibatch's image into self.x0n
-        elif self.wide:
-            self._x0n_image(X, M, stream(), idx)
+        return _ROUTES["act" if self.act_id else
+                       "panel" if self.panel else
+                       "trunk" if not partial and self.trunk_fused() else
+                       "fused2x" if two_equal and self.in_dim <= 64 and idx_is_none else
+                       "fused2" if two_equal and self.in_dim <= 32 else
+                       "wide" if self.wide else "input"]
+
+    def prepare_x0n(self, X: torch.Tensor, idx: Optional[torch.Tensor], M: int, partial: bool = False) -> _Route:
+        """Head of forward_trunk: have self.x0n ready for the first launch -- the (cached) image of X[idx], or no claim on what
+        that launch writes there.  Also run on its own in front of a captured optimiser step (HARL_GRAPH=1, graphs.py): the image
+        launch depends on a host-side cache (first step of an update: miss, later ones: hit) and a replayed graph repeats what
+        was captured, so the step must find the image cached (fused_args: the identity image, as "fused2x" reads it)."""
+        self._ensure_ws(M)
+        route = self._first_launch(idx is None, partial)
+        if route.image == "clobbers":
+            self._x0n_key = None
         else:
-            self._x0n_key = None  # harl_mlp_fwd_input may write self.x0n
+            self._x0n_image(X, M, stream(), idx)
+        return route
 
     def x0n_multi_item(self, X: torch.Tensor, M: int):
         """This network's entry in a one-launch build of several images (prepare_x0n_multi): (cache key, problem tuple of
         _lib.x0n_multi) when a full-buffer, identity-order pass over ``X`` reads the image that harl_mlp_x0n_wide(X, idx =
         None) builds and the one-launch kernel covers it (dense rows up to 64 wide) -- None otherwise, and the image is built
         where it is first asked for (recurrent nets, wider inputs, routes without an image, an empty data-parallel shard)."""
-        hs = self.hidden_sizes
-        if self.recurrent or M < 1 or not 1 <= self.in_dim <= 64 or X.dim() != 2 or X.shape[1] != self.in_dim or not X.is_contiguous():
-            return None
-        two_equal = len(hs) >= 2 and hs[0] == hs[1]
-        if not (self.act_id or self.panel or self.trunk_fused() or two_equal or self.wide):  # the routes of prepare_x0n
+        if (self.recurrent or M < 1 or not 1 <= self.in_dim <= 64 or X.dim() != 2 or X.shape[1] != self.in_dim or not X.is_contiguous()
+                or self._first_launch(True, False).image == "clobbers"):  # (a route without an image)
             return None
         self._ensure_ws(M)
         if self.x0n is None:
@@ -589,13 +602,12 @@ class _FlatNet(nn.Module):
         if self.recurrent:
             assert seq is not None and seq["L"] * seq["m_pad"] == M, "recurrent nets need the sequence layout"
             for_backward = True  # the fused 2-layer path may skip x_hat_1; keep it simple for recurrent nets
-        self._ensure_ws(M)
-        s = stream()
-        hs = self.hidden_sizes
-        first_hidden = 1
-        if self.act_id:
+        route = self.prepare_x0n(X, idx, M, upto is not None)
+        s, hs = stream(), self.hidden_sizes
+        first_hidden = 2 if route.kind in ("fused2x", "fused2") else 1
+        Wp, bp = self._packs[0]
+        if route.kind == "act":
             # activation other than ReLU: [Linear (raw GEMM) -> act + LayerNorm (element-wise)] per layer (mlp.py:25-38)
-            self._x0n_image(X, M, s, idx)
             for l, h in enumerate(hs):
                 Wp, bp = self._packs[l]
                 if l == 0:
@@ -606,20 +618,17 @@ class _FlatNet(nn.Module):
                 call("harl_act_ln_fwd", ptr(self.zraw), M, h, self.act_id, ptr(self.xh[l]), ptr(self.amean[l]), ptr(self.rstd[l]),
                      s, tag="act_ln_fwd")
             return
-        if self.panel:  # width 256: x0n image -> panel GEMMs (csrc/panel.hip)
-            self._x0n_image(X, M, s, idx)
+        if route.kind == "panel":  # width 256: x0n image -> panel GEMMs (csrc/panel.hip)
             for l in range(len(hs)):
                 Wp, bp = self._packs[l]
                 xin, kp, d = (self.x0n, self.kp0, self.in_dim) if l == 0 else (self.xh[l - 1], 256, 256)
                 call("harl_mlp_panel_fwd", ptr(xin), M, kp, ptr(Wp), d, ptr(bp), 256, ptr(self.xh[l]), ptr(self.rmask[l]),
                      ptr(self.rstd[l]), s, tag="fwd_panel")
             return
-        if upto is None and self.trunk_fused():
+        if route.kind == "trunk":
             # every layer (+ the input half of a fused GRU's gates) in ONE launch; forward-only passes write nothing but what
             # the next kernel reads (the three gate images, or x_hat_L)
             gates = self.recurrent and not self.gru_wide
-            Wp, bp = self._packs[0]
-            self._x0n_image(X, M, s, idx)
             pW, pb, pX, pM, pR = self._trunk_ptrs(bool(rnn_save), gates)
             gp = self.gru_pack if gates else None
             call("harl_mlp_fwd_trunk", ptr(self.x0n), M, self.kp0, ptr(Wp), self.in_dim, ptr(bp), 64, ptr(self.w1img),
@@ -628,32 +637,24 @@ class _FlatNet(nn.Module):
             if self.recurrent:
                 self.forward_rnn(seq, save=rnn_save, gates_done=gates)
             return
-        if len(hs) >= 2 and hs[0] == hs[1] and self.in_dim <= 64 and idx is None:
+        if route.kind == "fused2x":
             # layers 1+2 fused, from the x0n image: the rows are gathered and normalised ONCE per buffer (every epoch, log-prob
             # pass and line-search step over the same unmodified tensor reuses the image)
             (W1, b1), (W2, b2) = self._packs[0], self._packs[1]
-            self._x0n_image(X, M, s)
             call("harl_mlp_fwd_fused2x", ptr(self.x0n), M, ptr(W1), self.in_dim, ptr(b1), ptr(W2), ptr(b2), hs[0],
                  int(for_backward), ptr(self.xh[0]), ptr(self.rmask[0]), ptr(self.rstd[0]), ptr(self.xh[1]),
                  ptr(self.rmask[1]), ptr(self.rstd[1]), s, tag="fwd_fused2" if self.kp0 == 32 else "fwd_fused2_k64")
-            first_hidden = 2
-        elif len(hs) >= 2 and hs[0] == hs[1] and self.in_dim <= 32:
-            # layers 1+2 fused: x_hat_1 stays in registers; it is written out only if a backward pass follows
+        elif route.kind == "fused2":
+            # layers 1+2 fused: x_hat_1 stays in registers; it and the minibatch's image are written out only if a backward pass follows
             (W1, b1), (W2, b2) = self._packs[0], self._packs[1]
-            self._x0n_key = None  # this kernel writes the gathered minibatch's image into self.x0n
             call("harl_mlp_fwd_fused2", ptr(X), X.shape[1], ptr(idx), M, self.in_dim, ptr(W1), ptr(b1),
                  int(self.use_feature_normalization), ptr(W2), ptr(b2), hs[0], int(for_backward), ptr(self.xh[0]),
                  ptr(self.rmask[0]), ptr(self.rstd[0]), ptr(self.mu0), ptr(self.rstd0), ptr(self.xh[1]),
                  ptr(self.rmask[1]), ptr(self.rstd[1]), ptr(self.x0n) if for_backward else None, s, tag="fwd_fused2")
-            first_hidden = 2
-        elif self.wide:
-            Wp, bp = self._packs[0]
-            self._x0n_image(X, M, s, idx)
+        elif route.kind == "wide":
             call("harl_mlp_fwd_wide", ptr(self.x0n), M, self.kp0, ptr(Wp), self.in_dim, ptr(bp), hs[0], ptr(self.w1img),
                  ptr(self.xh[0]), ptr(self.rmask[0]), ptr(self.rstd[0]), s, tag="fwd_wide")
-        else:
-            Wp, bp = self._packs[0]
-            self._x0n_key = None  # (may write self.x0n)
+        else:  # "input" (may write self.x0n)
             call("harl_mlp_fwd_input", ptr(X), X.shape[1], ptr(idx), M, self.in_dim, ptr(Wp), ptr(bp),
                  int(self.use_feature_normalization), hs[0], ptr(self.xh[0]), ptr(self.rmask[0]), ptr(self.rstd[0]),
                  ptr(self.mu0), ptr(self.rstd0), ptr(self.x0n) if for_backward else None, s, tag="fwd_input")
@@ -698,7 +699,7 @@ class _FlatNet(nn.Module):
             return False
         if seq is not None or len(hs) < 2 or hs[-1] != hs[-2] or hs[-1] not in (64, 128) or self._layers()[-1][4] > 8:
             return False
-        two_fused = hs[0] == hs[1] and ((self.in_dim <= 64 and idx is None) or self.in_dim <= 32)  # forward_trunk's first launch
+        two_fused = self._first_launch(idx is None, True).kind in ("fused2x", "fused2")
         return len(hs) >= (3 if two_fused else 2) and bool(_lib.load().harl_update_supported(0, hs[-1], self._layers()[-1][4], 2 if isinstance(self, VNet) else 1))
 
     def fused_hybrid(self) -> bool:
@@ -881,15 +882,14 @@ class _FlatNet(nn.Module):
             cur = 1 - cur
         h0 = self.hidden_sizes[0]
         use_ln = self.use_feature_normalization
-        if fuse_dw1:
-            pass
-        elif self.x0n is not None:  # B = normalised inputs as written by the forward pass (ATL, zero-padded to kp0)
-            call("harl_mlp_dw_partials", ptr(self.dz[cur]), 0, 0, h0, ptr(self.x0n), 0, 0, None, None, None, self.kp0, M,
-                 ptr(self.part[po[0]:]), nwg, s, tag="dw_input")
-        else:
-            call("harl_mlp_dw_partials", ptr(self.dz[cur]), 0, 0, h0, ptr(X), 1, X.shape[1], ptr(idx),
-                 ptr(self.mu0) if use_ln else None, ptr(self.rstd0) if use_ln else None, self.in_dim, M,
-                 ptr(self.part[po[0]:]), nwg, s, tag="dw_input")
+        if not fuse_dw1:
+            if self.x0n is not None:  # B = normalised inputs as written by the forward pass (ATL, zero-padded to kp0)
+                call("harl_mlp_dw_partials", ptr(self.dz[cur]), 0, 0, h0, ptr(self.x0n), 0, 0, None, None, None, self.kp0, M,
+                     ptr(self.part[po[0]:]), nwg, s, tag="dw_input")
+            else:
+                call("harl_mlp_dw_partials", ptr(self.dz[cur]), 0, 0, h0, ptr(X), 1, X.shape[1], ptr(idx),
+                     ptr(self.mu0) if use_ln else None, ptr(self.rstd0) if use_ln else None, self.in_dim, M,
+                     ptr(self.part[po[0]:]), nwg, s, tag="dw_input")
         if side_pending:  # the weight gradients enqueued on the second stream
             e1 = self._bwd_ev[1]
             e1.record(self._bwd_side())

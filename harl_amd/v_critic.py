@@ -1,7 +1,6 @@
 """V critic on MI355X (reference: harl/algorithms/critics/v_critic.py:14-208)."""
 from __future__ import annotations
 
-import os
 from typing import Optional
 
 import torch
@@ -10,7 +9,7 @@ from . import _lib, graphs
 from ._lib import PS_STRIDE, call, ptr, stream
 from .buffers import OnPolicyCriticBufferEP, consume_randperm, minibatch_indices, rng_sync
 from .dist import Comm, local_minibatch_rows
-from .nets import FusedAdam, VNet, build_seq
+from .nets import FusedAdam, VNet, build_seq, routing_switches
 from .valuenorm import ValueNorm, _as_dev
 
 
@@ -113,12 +112,10 @@ class VCritic:
             self._graph_gen = net._ws_gen
         p = lambda t: 0 if t is None else t.data_ptr()  # noqa: E731
         g = opt.param_groups[0]
-        e = os.environ.get
         warm = (m, m_global, idx is None, vn is None, float(self.clip_param), bool(self.use_clipped_value_loss),
                 bool(self.use_huber_loss), float(self.huber_delta), float(self.value_loss_coef), bool(self.use_max_grad_norm),
                 float(self.max_grad_norm), tuple(g["betas"]), float(g["eps"]), float(g["weight_decay"]),
-                None if vn is None else vn.beta, e("HARL_FUSED_UPDATE"), e("HARL_BWD_FUSED"), e("HARL_BWD_K64"),
-                e("HARL_TRUNK_FUSED"))
+                None if vn is None else vn.beta) + routing_switches()
         key = warm + (p(share_obs), p(idx), p(value_preds), p(returns), None if vn is None else (p(vn.stats), p(vn._sums)),
                       p(self._info), p(net.flat_param), p(net.pack_arena), p(opt.exp_avg), p(opt._hyper_dev), opt._hyper_rows)
         G.run(warm, key, step, opt)

@@ -1,0 +1,259 @@
+"""Launch traces of whole train() calls, host side without a GPU: every C-ABI call of two ``prep_training(); train()`` rounds
+recorded instead of executed (the recorder of tests/test_multidiscrete_cpu.stub_kernels, a runner built like
+tests/test_hybrid_cpu._runner), in launch order, as [entry point, tag, arguments].  Arguments are reduced by their ctypes type
+in _lib.SIGNATURES: integers and floats literally, pointers to ``null`` or to the name of the persistent network tensor they
+point into (``actor0.xh[1]+0``; anything else is ``P``), elements of ctypes arrays likewise.  The names are the point: a change
+of the Python orchestration that hands another workspace to a kernel, or stops dropping the normalised-input image, changes the
+trace, while addresses and the allocator's reuse of them do not.
+
+    python tools/launch_trace.py --check tests/golden/launch_traces.json   # regenerate and compare (exit status 1: differs)
+    python tools/launch_trace.py --write tests/golden/launch_traces.json   # per configuration: names + tags, SHA-256 of the rest
+    python tools/launch_trace.py --full a.json                             # the full traces (about 400 KB)
+    python tools/launch_trace.py --diff a.json b.json                      # first differing call of two --full dumps
+
+tests/test_launch_trace_cpu.py runs the comparison of --check in the suite."""
+import argparse
+import ctypes
+import hashlib
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+import torch  # noqa: E402
+
+MODS = ("nets", "buffers", "happo", "hatrpo", "mappo", "v_critic", "valuenorm", "runner", "gru_wide")
+_SMAC = dict(obs=128, sobs=128)
+# name -> (hidden sizes, runner keywords, environment).  Between them: every first-layer launch of nets.forward_trunk, with
+# and without a row-index tensor (one / two minibatches), whole trunks and trunks that stop in front of harl_update_last_*.
+CONFIGS = {
+    "01_h128x2": ([128, 128], {}, {}),
+    "02_h128x2_obs40": ([128, 128], dict(obs=40, sobs=60), {}),
+    "03_h128x3": ([128, 128, 128], {}, {}),
+    "04_h128x3_mb2": ([128, 128, 128], dict(actor_num_mini_batch=2, critic_num_mini_batch=2), {}),
+    "05_h128_64": ([128, 64], {}, {}),
+    "06_h128_64_obs40": ([128, 64], dict(obs=40), {}),
+    "07_h64x2_obs128": ([64, 64], dict(_SMAC), {}),
+    "08_h64x2_obs128_layers": ([64, 64], dict(_SMAC), dict(HARL_TRUNK_FUSED="0")),
+    "09_h64x3_obs128_mb2": ([64, 64, 64], dict(_SMAC, actor_num_mini_batch=2, critic_num_mini_batch=2), {}),
+    "10_h256x2": ([256, 256], {}, {}),
+    "11_h128x2_tanh": ([128, 128], dict(activation_func="tanh"), {}),
+    "12_h64x2_obs128_gru": ([64, 64], dict(_SMAC, use_recurrent_policy=True, data_chunk_length=4), {}),
+    "13_h128x2_discrete100": ([128, 128], dict(discrete=100), {}),
+    "14a_h128x2_logp": ([128, 128], {}, dict(HARL_FUSED_UPDATE="logp")),
+    "14b_h128x2_bwd_fused": ([128, 128], {}, dict(HARL_BWD_FUSED="1")),
+}
+# the switches a configuration may set: cleared around every run, so that the caller's environment does not leak into a trace
+SWITCHES = ("HARL_FUSED_UPDATE", "HARL_BWD_FUSED", "HARL_BWD_K64", "HARL_TRUNK_FUSED", "HARL_GRAPH", "HARL_BWD_STREAMS",
+            "HARL_GRU128", "HARL_GRU_COMPOSED", "HARL_NWG", "HARL_X0N_MULTI", "HARL_FOLD_TABLE", "HARL_ALWAYS_FOLD",
+            "HARL_GRU_DW6", "HARL_TRUNK_DW_STREAM", "HARL_LIB")
+
+
+def make_runner(hidden, obs=19, sobs=11, act=3, discrete=0, T=8, N=8, A=2, **over):
+    """tests/test_hybrid_cpu._runner, plus a Discrete(``discrete``) action space."""
+    from harl_amd.runner import RUNNER_REGISTRY
+    from harl_amd.synthetic import Shapes, make_buffers
+    from tests.gpu_checks import Box, Discrete, default_args
+    a = default_args(hidden, ppo_epoch=2, critic_epoch=2, **over)
+    train = dict(n_rollout_threads=N, episode_length=T, use_valuenorm=True, use_linear_lr_decay=False,
+                 use_proper_time_limits=True, model_dir=None, eval_interval=25, use_eval=False, log_interval=1,
+                 num_env_steps=T * N * 2)
+    space = Discrete(discrete) if discrete else Box((act,))
+    r = RUNNER_REGISTRY["happo"](dict(algo="happo"), dict(train=train, model=dict(a), algo=dict(a)), dict(state_type="EP"),
+                                 obs_spaces=[Box((obs,))] * A, share_obs_space=Box((sobs,)), act_spaces=[space] * A,
+                                 device=torch.device("cpu"))
+    sh = Shapes(T=T, N=N, A=A, obs_dim=obs, share_obs_dim=sobs, act_dim=discrete or act, discrete=bool(discrete),
+                hidden_sizes=list(hidden))
+    d = make_buffers(sh, 4)
+    for ag in range(A):
+        b = r.actor_buffer[ag]
+        b.obs.copy_(torch.from_numpy(d.obs[ag]))
+        b.actions.copy_(torch.from_numpy(d.actions[ag]))
+        b.action_log_probs.copy_(torch.from_numpy(d.action_log_probs[ag]))
+    return r
+
+
+def networks(r):
+    """{owner name: network} of a runner: every actor's and the critic's."""
+    nets = {f"actor{i}": a.actor for i, a in enumerate(r.actor)}
+    nets["critic"] = r.critic.critic
+    return nets
+
+
+def _tensors(name, v, out):
+    if isinstance(v, torch.Tensor):
+        if v.numel():
+            out.append((v.data_ptr(), v.numel() * v.element_size(), name))
+    elif isinstance(v, list):
+        for i, x in enumerate(v):
+            _tensors(f"{name}[{i}]", x, out)
+    elif isinstance(v, dict):
+        for k, x in v.items():
+            _tensors(f"{name}[{k}]", x, out)
+
+
+class Recorder:
+    """Wraps the recorder ``stub_kernels`` installed: keeps the calls in launch order, reduced to what does not depend on
+    addresses."""
+
+    def __init__(self, monkeypatch):
+        from harl_amd import _lib
+        self.trace, self.nets = [], {}
+        self._inner, self._sig = _lib.call, _lib.SIGNATURES
+        monkeypatch.setattr(_lib, "call", self)
+        for mod in MODS:
+            m = __import__(f"harl_amd.{mod}", fromlist=["x"])
+            if hasattr(m, "call"):
+                monkeypatch.setattr(m, "call", self)
+
+    def __call__(self, name, *args, tag=None):
+        types = self._sig[name]
+        assert len(types) == len(args), (name, len(types), len(args))
+        names = self._names()
+        self.trace.append([name, tag, [self._arg(t, a, names) for t, a in zip(types, args)]])
+        return self._inner(name, *args, tag=tag)
+
+    def _names(self):
+        """(start, end, name) of every persistent tensor of the networks AS THEY ARE NOW (workspaces are reallocated when
+        a larger minibatch arrives), largest first: a view resolves to the arena it lives in."""
+        spans = []
+        for owner, net in self.nets.items():
+            for attr, v in vars(net).items():
+                if not attr.startswith("_parameters") and attr != "_modules":
+                    _tensors(f"{owner}.{attr}", v, spans)
+        return sorted(((p, p + n, nm) for p, n, nm in spans), key=lambda s: (s[0] - s[1], s[2]))
+
+    @staticmethod
+    def _resolve(p, names):
+        if not p:
+            return None
+        for lo, hi, nm in names:
+            if lo <= p < hi:
+                return f"{nm}+{p - lo}"
+        return "P"
+
+    def _arg(self, ctype, a, names):
+        if isinstance(a, ctypes.Array):
+            if a._type_ is ctypes.c_void_p:
+                return [self._resolve(x, names) for x in a]
+            return [x for x in a]
+        if ctype is ctypes.c_void_p:
+            return self._resolve(a, names)
+        return a if isinstance(a, (int, float)) else float(a)
+
+
+def run_config(name, monkeypatch, rounds=2):
+    """The trace of ``rounds`` x (prep_training(); train()) of configuration ``name``.  The caller has installed the stub
+    (the ``stub_kernels`` fixture) on the same ``monkeypatch``."""
+    hidden, kw, env = CONFIGS[name]
+    with monkeypatch.context() as mp:
+        for k in SWITCHES:
+            mp.delenv(k, raising=False)
+        for k, v in env.items():
+            mp.setenv(k, v)
+        rec = Recorder(mp)
+        torch.manual_seed(3)
+        r = make_runner(hidden, **kw)
+        rec.nets = networks(r)
+        del rec.trace[:]
+        for _ in range(rounds):
+            r.prep_training()
+            r.train()
+        return rec.trace
+
+
+def digest(trace):
+    return hashlib.sha256(json.dumps(trace, separators=(",", ":")).encode()).hexdigest()
+
+
+def summarise(traces):
+    """What the committed fixture keeps of the full traces (they are several hundred KB): per configuration every call's entry
+    point and tag in order -- as indices into ONE table of "entry:tag" names -- and a SHA-256 of the full trace."""
+    names = sorted({f"{c[0]}:{c[1] or ''}" for t in traces.values() for c in t})
+    at = {n: i for i, n in enumerate(names)}
+    return dict(names=names, traces={k: dict(calls=[at[f"{c[0]}:{c[1] or ''}"] for c in t], sha256=digest(t))
+                                     for k, t in traces.items()})
+
+
+def compare(want, got):
+    """Full traces ``got`` against the fixture ``want`` (summarise), as lines of text (empty: equal): per configuration the
+    first call whose entry point or tag differs, or that only the arguments do (then: first_difference of two --full dumps)."""
+    out, have = [], summarise(got)
+    for k in sorted(set(want["traces"]) | set(have["traces"])):
+        a, b = want["traces"].get(k), have["traces"].get(k)
+        if a is None or b is None:
+            out.append(f"{k}: only in the {'fixture' if b is None else 'tree'}")
+            continue
+        ca, cb = [want["names"][i] for i in a["calls"]], [have["names"][i] for i in b["calls"]]
+        if ca != cb:
+            i = next((i for i, (x, y) in enumerate(zip(ca, cb)) if x != y), min(len(ca), len(cb)))
+            out.append(f"{k}: call {i} of {len(ca)} / {len(cb)}: fixture {ca[i] if i < len(ca) else '(end)'}, "
+                       f"tree {cb[i] if i < len(cb) else '(end)'}")
+        elif a["sha256"] != b["sha256"]:
+            out.append(f"{k}: the same {len(ca)} calls with other arguments (sha256 {b['sha256'][:16]}, fixture {a['sha256'][:16]}): "
+                       "write --full dumps of both trees and compare them with --diff")
+    return out
+
+
+def first_difference(ta, tb):
+    """The first differing call of every configuration of two sets of full traces, as lines of text."""
+    out = []
+    for k in sorted(set(ta) | set(tb)):
+        a, b = ta.get(k, []), tb.get(k, [])
+        i = next((i for i, (x, y) in enumerate(zip(a, b)) if x != y), None)
+        if i is None and len(a) != len(b):
+            i = min(len(a), len(b))
+        if i is not None:
+            out.append(f"{k}: call {i} of {len(a)} / {len(b)}\n  a: {a[i] if i < len(a) else '(end)'}\n"
+                       f"  b: {b[i] if i < len(b) else '(end)'}")
+    return out
+
+
+def normalise(traces):
+    """Through JSON and back, as the fixture went: tags and NULLs as None, every sequence a list."""
+    return json.loads(json.dumps(traces))
+
+
+def all_traces():
+    import pytest
+    from tests.test_multidiscrete_cpu import stub_kernels
+    fixture = getattr(stub_kernels, "__wrapped__", None) or stub_kernels.__pytest_wrapped__.obj
+    with pytest.MonkeyPatch.context() as mp:
+        fixture(mp)
+        return {k: run_config(k, mp) for k in CONFIGS}
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    g = ap.add_mutually_exclusive_group(required=True)
+    g.add_argument("--check", metavar="FIXTURE", help="regenerate the traces and compare them with FIXTURE")
+    g.add_argument("--write", metavar="FIXTURE", help="write the fixture of this tree: names, tags and a SHA-256 per configuration")
+    g.add_argument("--full", metavar="OUT", help="write the full traces of this tree")
+    g.add_argument("--diff", nargs=2, metavar=("A", "B"), help="the first differing call of two --full dumps")
+    a = ap.parse_args()
+    lines = []
+    if a.diff:
+        with open(a.diff[0]) as fa, open(a.diff[1]) as fb:
+            lines = first_difference(json.load(fa), json.load(fb))
+    else:
+        traces = normalise(all_traces())
+        if a.full:
+            with open(a.full, "w") as f:
+                json.dump(traces, f, separators=(",", ":"))
+        elif a.write:
+            fx = summarise(traces)
+            with open(a.write, "w") as f:  # one configuration per line
+                f.write('{"names": ' + json.dumps(fx["names"]) + ',\n "traces": {\n' + ",\n".join(
+                    f'  {json.dumps(k)}: {json.dumps(t, separators=(",", ":"))}' for k, t in fx["traces"].items()) + "\n}}\n")
+        else:
+            with open(a.check) as f:
+                lines = compare(json.load(f), traces)
+    print("\n".join(lines) if lines else "no difference")
+    return 1 if lines else 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
