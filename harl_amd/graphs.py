@@ -25,6 +25,7 @@ from typing import Callable, Dict, Hashable
 import torch
 
 from . import _lib
+from .configs import bwd_streams, trunk_dw_stream
 
 _capturing = False
 
@@ -40,9 +41,9 @@ def capturing() -> bool:
 
 def launches_capturable(device: torch.device) -> bool:
     """Graph mode is on, the device is a GPU, launches are not bracketed by timing events (bench.py's instrumented steps) and
-    no variant that puts a second stream INSIDE an optimiser step is selected."""
-    return (enabled() and device.type == "cuda" and not _lib._timing_on
-            and os.environ.get("HARL_BWD_STREAMS", "0") != "1" and os.environ.get("HARL_TRUNK_DW_STREAM", "0") != "1")
+    no variant that puts a second stream INSIDE an optimiser step is selected (the variable being set is enough, whatever the
+    network: nets._backward_route decides per network)."""
+    return (enabled() and device.type == "cuda" and not _lib._timing_on and not bwd_streams() and not trunk_dw_stream())
 
 
 class GraphedStep:

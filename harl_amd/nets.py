@@ -22,7 +22,7 @@ import torch.nn as nn
 from . import _lib
 from . import graphs as _graphs
 from ._lib import DHEAD_LD, PS_STRIDE, SLAB, call, ptr, stream
-from .configs import CAT_WIDE_REFUSALS
+from .configs import CAT_WIDE_REFUSALS, bwd_k64, bwd_streams, gru_dw6, trunk_dw_stream
 
 SUPPORTED_WIDTHS = (64, 128, 256)
 # models_tools.py:28-50; ids of csrc/elementwise.hip (0 = the fused ReLU kernels)
@@ -69,6 +69,15 @@ _Route = NamedTuple("_Route", [("kind", str), ("image", str)])
 _ROUTES = {k: _Route(k, im) for k, im in dict(act="cached", panel="cached", trunk="cached", fused2x="cached_identity",
                                               fused2="clobbers", wide="cached", input="clobbers").items()}
 
+# _FlatNet._backward_route.  family: "trunk" (the 64-wide trunk in one launch) | "panel" | "act" | "layers";  gru: "none" |
+# "fused" (harl_gru_bwd) | "composed" (gru_wide.backward);  the layer loop -- hidden: what a 128 x 128 layer takes, "full"
+# (harl_mlp_bwd_dx_dw) | "side" (dx, the weight gradient on the second stream) | "plain" (dw, then dx; _hidden_launch narrows
+# it per layer), fill: harl_mlp_bwd_dx_dw's argument, dw1: the first-layer gradient "fused" into layer 1's dx launch | from the
+# "image" self.x0n | from the gathered "rows";  the one-launch trunk -- gates_side / gates_dw6: the gate blocks' gradients on
+# the second stream / through harl_gru_dw6;  one_wg_per_cu: every weight gradient comes out of a one-workgroup-per-CU launch
+_BwdRoute = NamedTuple("_BwdRoute", [("family", str), ("gru", str), ("hidden", str), ("fill", int), ("dw1", str),
+                                     ("gates_side", bool), ("gates_dw6", bool), ("one_wg_per_cu", bool)])
+
 
 def routing_switches() -> tuple:
     return tuple(map(os.environ.get, ROUTING_SWITCHES))
@@ -95,12 +104,6 @@ def prepare_x0n_multi(items) -> int:
     for net, X, it in todo:
         net._x0n_key, net._x0n_src = it[0], (X, None)
     return len(todo)
-
-
-def _bwd_streams() -> bool:
-    """``HARL_BWD_STREAMS=1``: the hidden layers' weight-gradient launches go to a second stream next to the backward-dx
-    launches (nets.backward_trunk; the C side picks the register-lean dx kernel under the same variable)."""
-    return os.environ.get("HARL_BWD_STREAMS", "0") == "1"
 
 
 def _space_shape(space) -> Tuple[int, ...]:
@@ -174,6 +177,9 @@ class _FlatNet(nn.Module):
             raise NotImplementedError("activation functions other than relu: feed-forward MLPs of width 64 / 128 with inputs <= 512")
         self.in_dim = in_dim
         self.wide = 32 < in_dim <= 512  # first layer through the cached x0n image (csrc/wide.hip); <= 32: fused 2-layer kernel
+        # the normalised inputs as an ATL image of kp0 columns (self.x0n, _ensure_ws): inputs up to 512 wide
+        self.kp0 = ((in_dim + 31) // 32) * 32
+        self.has_x0n = in_dim <= 64 or self.wide
         self._x0n_key = None
         self._x0n_force = False  # build the image whatever the cache says (graphs.py: several buffers inside ONE captured step)
         self.md = False  # MultiDiscrete heads (StochasticPolicy)
@@ -347,7 +353,7 @@ class _FlatNet(nn.Module):
             dwp_off += elems
         self._table_rows = rows
         self.n_entries = len(rows)
-        self._ws_gen = getattr(self, "_ws_gen", 0) + 1  # (captured optimiser steps hold the arenas' addresses: graphs.py)
+        self._new_addresses()
         self.pack_arena = torch.zeros(pack_off, dtype=torch.float32, device=dev)
         # the dense folded gradients live at the head of the data-parallel all-reduce message: [dwp | 4 fixed-grid scalar pieces] (dist.py)
         self.dwp_msg = torch.zeros(dwp_off + 4 * PS_STRIDE, dtype=torch.float32, device=dev)
@@ -400,11 +406,18 @@ class _FlatNet(nn.Module):
         self._fold_version = ver
 
     # ---- workspaces -------------------------------------------------------------------------
+    def _new_addresses(self) -> None:
+        """pack_arena or the workspaces are about to get new storage (_build_tables, _ensure_ws): whatever holds their device
+        addresses goes with the old one -- the captured optimiser steps (graphs.py; their owners compare _ws_gen) and the
+        ctypes pointer arrays of the one-launch trunk (_trunk_ptrs, _backward_trunk_fused)."""
+        self._ws_gen = getattr(self, "_ws_gen", 0) + 1
+        self._trunk_cache = {}
+
     def _ensure_ws(self, M: int) -> None:
         if M <= self._max_rows:
             return
         dev = self.device_
-        self._ws_gen = getattr(self, "_ws_gen", 0) + 1  # every workspace below gets a new address
+        self._new_addresses()  # every workspace below gets a new address
         n_slabs = (M + SLAB - 1) // SLAB
         mp = n_slabs * SLAB
         f32, u32 = torch.float32, torch.int32
@@ -414,9 +427,8 @@ class _FlatNet(nn.Module):
         self.mu0 = torch.empty(mp, dtype=f32, device=dev)
         self.rstd0 = torch.empty(mp, dtype=f32, device=dev)
         # narrow inputs: the forward pass leaves the normalised inputs behind as an ATL image for the dW_1 kernel
-        self.kp0 = ((self.in_dim + 31) // 32) * 32
         self._x0n_key = None
-        self.x0n = torch.empty(mp * self.kp0, dtype=f32, device=dev) if (self.in_dim <= 64 or self.wide) else None
+        self.x0n = torch.empty(mp * self.kp0, dtype=f32, device=dev) if self.has_x0n else None
         self.w1img = (torch.empty(3 * self.hidden_sizes[0] * self.kp0 // 2, dtype=f32, device=dev)
                       if (self.wide or self.act_id) else None)
         hmax = max(self.hidden_sizes)
@@ -426,7 +438,6 @@ class _FlatNet(nn.Module):
             self.ones_mask = torch.full((n_slabs * 64 * 2,), -1, dtype=u32, device=dev)
         # ping-pong, ATL; a third one where the one-launch trunk backward keeps every layer's dz for the weight-gradient launch
         self.dz = [torch.empty(mp * hmax, dtype=f32, device=dev) for _ in range(3 if len(self.hidden_sizes) == 3 and self.trunk_fused() else 2)]
-        self._trunk_cache = {}
         # head gradients for the separate dW pass: row-major [mp][32], or the ATL(64) image of a 33..64-way Categorical head
         self.wide_head = (not self.grouped) and self._layers()[-1][4] > 32
         self.dhead = torch.zeros(mp * (64 if self.wide_head else DHEAD_LD), dtype=f32, device=dev)
@@ -443,8 +454,7 @@ class _FlatNet(nn.Module):
         # ... and 256 rows when every weight gradient of this network comes out of a one-workgroup-per-CU launch (the fused forward's
         # head gradient, harl_mlp_bwd_dx_dw for the trunk): the other 256 rows would only be cleared by them and read back by
         # the combine (~22 MB each way per optimiser step at the 3-agent headline shapes)
-        if (not nwg_env and _bwd_fused_mode(M) == "1" and len(self.hidden_sizes) >= 2 and all(h == 128 for h in self.hidden_sizes)
-                and ((self.in_dim + 31) // 32) * 32 == 32 and not (self.recurrent or self.grouped or self.act_id or self.panel)):
+        if not nwg_env and self._backward_route(M).one_wg_per_cu:
             nwg_cap = 256
         self.n_wg = max(1, min(nwg_cap, n_iter))
         part_off, rows = 0, [list(r) for r in self._table_rows]
@@ -507,7 +517,7 @@ class _FlatNet(nn.Module):
                 and 2 <= len(hs) <= 3 and all(h == 64 for h in hs))
 
     def _trunk_ptrs(self, save: bool, gates: bool):
-        """ctypes pointer arrays of harl_mlp_fwd_trunk for the current workspaces (cached: they change with _ensure_ws only)."""
+        """ctypes pointer arrays of harl_mlp_fwd_trunk for the current workspaces (cached until their storage changes: _new_addresses)."""
         key = (save, gates, self._max_rows)
         hit = self._trunk_cache.get(key)
         if hit is None:
@@ -755,98 +765,162 @@ class _FlatNet(nn.Module):
                        head_dw_done: bool = False) -> None:
         """``head_dw_done``: the loss kernel already wrote the head's weight-gradient partials (fused path)."""
         s = stream()
-        L = len(self.hidden_sizes)
-        nwg = self.n_wg
-        po = self._part_offs
-        hdim = self._layers()[-1][4]
-        fx, _, _, fh = self.feat()
-        # head: dW_head' = dhead^T x_hat_L   (x_hat_L = GRU output for recurrent nets)
-        if self.grouped:
-            self.md_backward(M)
-        elif not head_dw_done:
-            if self.wide_head:  # ATL(64) image: an ordinary two-operand weight-gradient GEMM (partial layout dWp[64][fh] | dbp[64])
-                call("harl_mlp_dw_partials", ptr(self.dhead), 0, 0, 64, ptr(fx), 0, 0, None, None, None, fh, M,
-                     ptr(self.part[po[-1]:]), nwg, s, tag="dw_head")
-            elif self.panel:  # 256-wide trunk (HATRPO's separate head-gradient pass; HAPPO's loss kernel fuses it)
-                call("harl_head_dw_rows256", ptr(self.dhead), M, hdim, ptr(fx), ptr(self.part[po[-1]:]), nwg, s, tag="dw_head")
-            else:
-                call("harl_mlp_dw_partials", ptr(self.dhead), 1, DHEAD_LD, hdim, ptr(fx), 0, 0, None, None, None, fh, M,
-                     ptr(self.part[po[-1]:]), nwg, s, tag="dw_head")
+        self._backward_head(M, head_dw_done, s)
+        route = self._backward_route(M)
+        if route.family == "trunk":
+            self._backward_trunk_fused(M, seq, s, route)
+        elif route.family == "panel":
+            self._backward_panel(M, s)
+        elif route.family == "act":
+            self._backward_act(M, s)
+        else:
+            # self.dz[cur] holds dz of the last MLP layer: d(loss)/d(h) in dz[0] went through the GRU into dz[1], if there is one
+            cur = 0 if route.gru == "none" else self._backward_gru(M, seq, s, route)
+            self._backward_layers(X, idx, M, cur, s, route)
+        # deterministic fixed-order combine of every entry's per-workgroup partials, one launch
+        self._combine_partials(s)
+
+    def _backward_route(self, M: int) -> _BwdRoute:
+        """How a backward over ``M`` rows is launched (_BwdRoute above): backward_trunk dispatches on this, the route's methods
+        ask it instead of the switches, _ensure_ws takes the 256-row cap of the partial arena from it.  Order of precedence: the
+        one-launch 64-wide trunk (not behind a composed GRU), the 256-wide panels, the non-ReLU composition, else the layer
+        loop.  Like _first_launch it launches and allocates nothing: comparisons, and every switch read at most once (the
+        layer loop's only: HARL_BWD_FUSED, HARL_BWD_K64, HARL_BWD_STREAMS; the trunk's only: HARL_TRUNK_DW_STREAM, HARL_GRU_DW6)."""
+        hs = self.hidden_sizes
+        L, cuda = len(hs), self.device_.type == "cuda"
+        gru = "none" if not self.recurrent else "composed" if self.gru_wide else "fused"
         if self.trunk_fused() and not self.gru_wide:
-            return self._backward_trunk_fused(M, seq, s)
-        cur = 0  # self.dz[cur] holds dz of the last MLP layer (non-recurrent) / d(loss)/d(h) (recurrent)
-        if self.recurrent:
-            gp, sv, dg = self.gru_pack, self.rnn_saved, self.rnn_dgate
-            H = self.hidden_sizes[-1]
-            if self.gru_wide:
-                from . import gru_wide
-                gru_wide.backward(self, seq)
-            else:
-                call("harl_gru_bwd", ptr(self.dz[0]), ptr(seq["mask_rows"]), ptr(gp["Wih"]), ptr(gp["Whh"]), ptr(sv[0]),
-                     ptr(sv[1]), ptr(sv[2]), ptr(sv[3]), ptr(sv[4]), H, seq["L"], seq["m_pad"], ptr(self.xh[-1]),
-                     ptr(self.rmask[-1]), ptr(self.rstd[-1]), ptr(dg[0]), ptr(dg[1]), ptr(dg[2]), ptr(dg[3]), ptr(self.dz[1]), s,
-                     tag="gru_bwd")
-            # the six gate blocks in ONE launch: W_ih' blocks d gi_g^T x_hat_mlp (g = r, z, n), W_hh blocks d gh_g^T h~ (dhn for n)
-            import ctypes as C
-            for gl in range(self.recurrent_n):  # layer gl reads x_hat of the MLP (gl = 0) or the raw output of layer gl - 1
-                dg_, sv_ = self.rnn_dgate_l[gl], self.rnn_saved_l[gl]
-                xin = self.xh[-1] if gl == 0 else self.rnn_hraw_l[gl - 1]
-                a6 = (C.c_void_p * 6)(*[ptr(t) for t in (dg_[0], dg_[1], dg_[2], dg_[0], dg_[1], dg_[3])])
-                b6 = (C.c_void_p * 6)(*([ptr(xin)] * 3 + [ptr(sv_[0])] * 3))
-                p6 = (C.c_void_p * 6)(*[ptr(self.part[po[L + 6 * gl + k]:]) for k in range(6)])
-                call("harl_mlp_dw_partials_multi", 6, a6, b6, p6, H, H, M, nwg, s, tag="dw_gru")
-            cur = 1
-        if self.panel:  # width 256 (csrc/panel.hip): per layer dW = dz^T x_hat_prev, then dz_prev through the panel GEMM
-            for l in range(L - 1, -1, -1):
-                b_in, k_in = (self.x0n, self.kp0) if l == 0 else (self.xh[l - 1], 256)
-                call("harl_mlp_dw_partials", ptr(self.dz[cur]), 0, 0, 256, ptr(b_in), 0, 0, None, None, None, k_in, M,
-                     ptr(self.part[po[l]:]), nwg, s, tag="dw_hidden" if l else "dw_input")
-                if l > 0:
-                    Wp, _ = self._packs[l]
-                    call("harl_mlp_panel_bwd", ptr(self.dz[cur]), ptr(self.xh[l - 1]), ptr(self.rmask[l - 1]),
-                         ptr(self.rstd[l - 1]), M, 256, 256, ptr(Wp), ptr(self.dz[1 - cur]), s, tag="bwd_panel")
-                    cur = 1 - cur
-            self._combine_partials(s)
-            return
-        if self.act_id:
-            # activation other than ReLU: the loss kernel / harl_mlp_bwd_dx were handed an all-ones mask, so self.dz holds the
-            # LayerNorm backward d(loss)/d(act(z)); harl_act_bwd multiplies by act'(z) in place (csrc/elementwise.hip)
-            hs = self.hidden_sizes
-            call("harl_act_bwd", ptr(self.dz[cur]), ptr(self.xh[L - 1]), ptr(self.amean[L - 1]), ptr(self.rstd[L - 1]), M, hs[L - 1],
-                 self.act_id, s, tag="act_bwd")
-            for l in range(L - 1, 0, -1):
-                ho, hi = hs[l], hs[l - 1]
-                call("harl_mlp_dw_partials", ptr(self.dz[cur]), 0, 0, ho, ptr(self.xh[l - 1]), 0, 0, None, None, None, hi, M,
-                     ptr(self.part[po[l]:]), nwg, s, tag="dw_hidden")
-                Wp, _ = self._packs[l]
-                call("harl_mlp_bwd_dx", ptr(self.dz[cur]), ptr(self.xh[l - 1]), ptr(self.ones_mask), ptr(self.rstd[l - 1]), M, ho,
-                     hi, ptr(Wp), ptr(self.dz[1 - cur]), None, 0, None, 0, s, tag="bwd_dx")
-                cur = 1 - cur
-                call("harl_act_bwd", ptr(self.dz[cur]), ptr(self.xh[l - 1]), ptr(self.amean[l - 1]), ptr(self.rstd[l - 1]), M, hi,
-                     self.act_id, s, tag="act_bwd")
-            call("harl_mlp_dw_partials", ptr(self.dz[cur]), 0, 0, hs[0], ptr(self.x0n), 0, 0, None, None, None, self.kp0, M,
-                 ptr(self.part[po[0]:]), nwg, s, tag="dw_input")
-            self._combine_partials(s)
-            return
+            # the six gate blocks as ONE problem (harl_gru_dw6) pay from 160 000 rows; HARL_GRU_DW6=1 / 0 force it on / off
+            side = self.recurrent and cuda and trunk_dw_stream()
+            g6 = gru_dw6()
+            return _BwdRoute("trunk", gru, "plain", 1, "image", side,
+                             self.recurrent and not side and (g6 == "1" or (g6 == "auto" and M >= 160000)), False)
+        if self.panel or self.act_id:
+            return _BwdRoute("panel" if self.panel else "act", gru, "plain", 1, "image", False, False, False)
+        mode = _bwd_fused_mode(M)
+        sq1 = L >= 2 and hs[0] == 128 and hs[1] == 128
         # first-layer weight gradient fused into the last bwd_dx (needs the ones column of x0n: in_dim < kp0)
-        fuse_dw1 = L >= 2 and self.x0n is not None and self.in_dim < self.kp0 and self.kp0 <= 64
-        bwd_mode = _bwd_fused_mode(M)
-        side_pending = False
-        if (bwd_mode != "0" and fuse_dw1 and self.kp0 == 64 and L >= 2 and self.hidden_sizes[0] == 128 and self.hidden_sizes[1] == 128
-                and os.environ.get("HARL_BWD_K64", "0") == "1"):
+        fuse_dw1 = L >= 2 and self.has_x0n and self.in_dim < self.kp0 and self.kp0 <= 64
+        if mode != "0" and fuse_dw1 and self.kp0 == 64 and sq1 and bwd_k64():
             # 33..64 inputs (the MPE critic's 54): the first-layer gradient of a 64-wide image does not fit the register file next
             # to the layer's own gradient -- one-launch backward that WRITES dz_1, then the two-operand weight-gradient launch
             fuse_dw1 = False
+        # (a second stream only next to the layer kernels: under the one-launch modes every layer it could take is "full")
+        hidden = "full" if mode != "0" else "side" if (L >= 2 and cuda and bwd_streams()) else "plain"
+        # 32 inputs count although their first-layer gradient is a launch of its own (no ones column to fuse it): the cap
+        # decides n_wg and with it the order of every sum, so it stays as it was measured
+        one_wg = (mode == "1" and gru == "none" and not self.grouped and L >= 2 and all(h == 128 for h in hs) and self.kp0 == 32)
+        return _BwdRoute("layers", gru, hidden, 0 if mode == "nofill" else 2 if mode == "fill" else 1,
+                         "fused" if fuse_dw1 else "image" if self.has_x0n else "rows", False, False, one_wg)
+
+    def _hidden_launch(self, route: _BwdRoute, l: int) -> str:
+        """The route's answer for hidden layer ``l`` (1-based input side: Linear l + 1 of the layer loop): route.hidden for a
+        128 x 128 layer, unless it carries the first-layer gradient of a 64-wide image; "plain" otherwise."""
+        hs = self.hidden_sizes
+        if hs[l] == 128 and hs[l - 1] == 128 and not (l == 1 and route.dw1 == "fused" and self.kp0 == 64):
+            return route.hidden
+        return "plain"
+
+    def _dw_atl(self, a: torch.Tensor, ho: int, b: torch.Tensor, k: int, M: int, entry: int, s, tag: str) -> None:
+        """Weight-gradient partials of table entry ``entry``, dW' = a^T b from two ATL images (``ho`` / ``k`` columns wide)."""
+        call("harl_mlp_dw_partials", ptr(a), 0, 0, ho, ptr(b), 0, 0, None, None, None, k, M,
+             ptr(self.part[self._part_offs[entry]:]), self.n_wg, s, tag=tag)
+
+    def _backward_head(self, M: int, head_dw_done: bool, s) -> None:
+        """dW_head' = dhead^T x_hat_L   (x_hat_L = GRU output for recurrent nets)"""
+        if self.grouped:
+            self.md_backward(M)
+        elif not head_dw_done:
+            fx, _, _, fh = self.feat()
+            if self.wide_head:  # ATL(64) image: an ordinary two-operand weight-gradient GEMM (partial layout dWp[64][fh] | dbp[64])
+                self._dw_atl(self.dhead, 64, fx, fh, M, -1, s, "dw_head")
+            elif self.panel:  # 256-wide trunk (HATRPO's separate head-gradient pass; HAPPO's loss kernel fuses it)
+                call("harl_head_dw_rows256", ptr(self.dhead), M, self._layers()[-1][4], ptr(fx), ptr(self.part[self._part_offs[-1]:]),
+                     self.n_wg, s, tag="dw_head")
+            else:
+                call("harl_mlp_dw_partials", ptr(self.dhead), 1, DHEAD_LD, self._layers()[-1][4], ptr(fx), 0, 0, None, None, None, fh, M,
+                     ptr(self.part[self._part_offs[-1]:]), self.n_wg, s, tag="dw_head")
+
+    def _gru_bwd(self, seq: dict, dx: Optional[torch.Tensor], s) -> None:
+        """The fused GRU's recurrence backwards: d(loss)/d(h) in self.dz[0] -> the gate gradients self.rnn_dgate and, with
+        ``dx``, the gradient at the last MLP layer's pre-activation (None: the one-launch trunk does the input side)."""
+        gp, sv, dg = self.gru_pack, self.rnn_saved, self.rnn_dgate
+        call("harl_gru_bwd", ptr(self.dz[0]), ptr(seq["mask_rows"]), ptr(gp["Wih"]), ptr(gp["Whh"]), ptr(sv[0]),
+             ptr(sv[1]), ptr(sv[2]), ptr(sv[3]), ptr(sv[4]), self.hidden_sizes[-1], seq["L"], seq["m_pad"], ptr(self.xh[-1]),
+             ptr(self.rmask[-1]), ptr(self.rstd[-1]), ptr(dg[0]), ptr(dg[1]), ptr(dg[2]), ptr(dg[3]), ptr(dx), s, tag="gru_bwd")
+
+    def _gate_operands(self, gl: int):
+        """The six weight-gradient problems of GRU layer ``gl`` as (A images, B images): W_ih' blocks d gi_g^T x_in (g = r, z,
+        n), W_hh blocks d gh_g^T h~ (dhn for n); x_in = x_hat of the MLP (gl = 0) or the raw output of layer gl - 1."""
+        dg, sv = self.rnn_dgate_l[gl], self.rnn_saved_l[gl]
+        xin = self.xh[-1] if gl == 0 else self.rnn_hraw_l[gl - 1]
+        return (dg[0], dg[1], dg[2], dg[0], dg[1], dg[3]), (xin, xin, xin, sv[0], sv[0], sv[0])
+
+    def _backward_gru(self, M: int, seq: dict, s, route: _BwdRoute) -> int:
+        """The GRU in front of the layer loop: its recurrence (fused or composed) leaves dz of the last MLP layer in self.dz[1]
+        -- the index is returned -- then the six gate blocks of every GRU layer in ONE launch each."""
+        import ctypes as C
+        if route.gru == "composed":
+            from . import gru_wide
+            gru_wide.backward(self, seq)
+        else:
+            self._gru_bwd(seq, self.dz[1], s)
+        L, H, po = len(self.hidden_sizes), self.hidden_sizes[-1], self._part_offs
+        for gl in range(self.recurrent_n):
+            a, b = self._gate_operands(gl)
+            a6 = (C.c_void_p * 6)(*[ptr(t) for t in a])
+            b6 = (C.c_void_p * 6)(*[ptr(t) for t in b])
+            p6 = (C.c_void_p * 6)(*[ptr(self.part[po[L + 6 * gl + k]:]) for k in range(6)])
+            call("harl_mlp_dw_partials_multi", 6, a6, b6, p6, H, H, M, self.n_wg, s, tag="dw_gru")
+        return 1
+
+    def _backward_panel(self, M: int, s) -> None:
+        """Width 256 (csrc/panel.hip): per layer dW = dz^T x_hat_prev, then dz_prev through the panel GEMM."""
+        cur = 0
+        for l in range(len(self.hidden_sizes) - 1, -1, -1):
+            b_in, k_in = (self.x0n, self.kp0) if l == 0 else (self.xh[l - 1], 256)
+            self._dw_atl(self.dz[cur], 256, b_in, k_in, M, l, s, "dw_hidden" if l else "dw_input")
+            if l > 0:
+                Wp, _ = self._packs[l]
+                call("harl_mlp_panel_bwd", ptr(self.dz[cur]), ptr(self.xh[l - 1]), ptr(self.rmask[l - 1]),
+                     ptr(self.rstd[l - 1]), M, 256, 256, ptr(Wp), ptr(self.dz[1 - cur]), s, tag="bwd_panel")
+                cur = 1 - cur
+
+    def _backward_act(self, M: int, s) -> None:
+        """Activation other than ReLU: the loss kernel / harl_mlp_bwd_dx were handed an all-ones mask, so self.dz holds the
+        LayerNorm backward d(loss)/d(act(z)); harl_act_bwd multiplies by act'(z) in place (csrc/elementwise.hip)."""
+        hs = self.hidden_sizes
+        L, cur = len(hs), 0
+        call("harl_act_bwd", ptr(self.dz[cur]), ptr(self.xh[L - 1]), ptr(self.amean[L - 1]), ptr(self.rstd[L - 1]), M, hs[L - 1],
+             self.act_id, s, tag="act_bwd")
+        for l in range(L - 1, 0, -1):
+            ho, hi = hs[l], hs[l - 1]
+            self._dw_atl(self.dz[cur], ho, self.xh[l - 1], hi, M, l, s, "dw_hidden")
+            Wp, _ = self._packs[l]
+            call("harl_mlp_bwd_dx", ptr(self.dz[cur]), ptr(self.xh[l - 1]), ptr(self.ones_mask), ptr(self.rstd[l - 1]), M, ho,
+                 hi, ptr(Wp), ptr(self.dz[1 - cur]), None, 0, None, 0, s, tag="bwd_dx")
+            cur = 1 - cur
+            call("harl_act_bwd", ptr(self.dz[cur]), ptr(self.xh[l - 1]), ptr(self.amean[l - 1]), ptr(self.rstd[l - 1]), M, hi,
+                 self.act_id, s, tag="act_bwd")
+        self._dw_atl(self.dz[cur], hs[0], self.x0n, self.kp0, M, 0, s, "dw_input")
+
+    def _backward_layers(self, X: torch.Tensor, idx: Optional[torch.Tensor], M: int, cur: int, s, route: _BwdRoute) -> None:
+        """The layer loop: hidden Linears top down from dz in self.dz[``cur``], each as the route says (_hidden_launch), then the
+        first-layer gradient where the last dx launch did not carry it."""
+        L, nwg, po = len(self.hidden_sizes), self.n_wg, self._part_offs
+        fuse_dw1 = route.dw1 == "fused"
+        side_pending = False
         for l in range(L - 1, 0, -1):
             ho, hi = self.hidden_sizes[l], self.hidden_sizes[l - 1]
             Wp, _ = self._packs[l]
             dw1_here = l == 1 and fuse_dw1
-            if bwd_mode != "0" and ho == 128 and hi == 128 and (not dw1_here or self.kp0 == 32):
+            launch = self._hidden_launch(route, l)
+            if launch == "full":
                 # the whole backward of this layer in ONE launch (round 5): dz and x_hat_{l-1} cross HBM once for dx AND dW'
                 call("harl_mlp_bwd_dx_dw", ptr(self.dz[cur]), ptr(self.xh[l - 1]), ptr(self.rmask[l - 1]), ptr(self.rstd[l - 1]), M,
                      ho, hi, ptr(Wp), None if dw1_here else ptr(self.dz[1 - cur]), ptr(self.x0n) if dw1_here else None,
                      self.kp0 if dw1_here else 0, ptr(self.part[po[0]:]) if dw1_here else None, ptr(self.part[po[l]:]), nwg,
-                     {"nofill": 0, "fill": 2}.get(bwd_mode, 1), s, tag="bwd_full_dw1" if dw1_here else "bwd_full")
+                     route.fill, s, tag="bwd_full_dw1" if dw1_here else "bwd_full")
                 cur = 1 - cur
                 continue
             # HARL_BWD_STREAMS=1: the layer's weight gradient goes to a SECOND stream, next to the backward-dx launch -- both read
@@ -854,9 +928,8 @@ class _FlatNet(nn.Module):
             # per CU (96 KiB of LDS, the register-lean instantiation) leaves room for one weight-gradient workgroup, so the two
             # kernels share every CU and fill each other's stalls; the other order would park two weight-gradient workgroups on
             # every CU and the dx kernel behind them.
-            two = (_bwd_streams() and ho == 128 and hi == 128 and self.device_.type == "cuda"
-                   and (not (l == 1 and fuse_dw1) or self.kp0 == 32))
-            if side_pending and not (l == 1 and fuse_dw1):
+            two = launch == "side"
+            if side_pending and not dw1_here:
                 # this layer's dx launch WRITES dz[1 - cur] -- the buffer the previous layer's weight-gradient launch on the side
                 # stream still reads (L >= 3 with an unfused first-layer gradient): order it behind that launch
                 torch.cuda.current_stream(self.device_).wait_event(self._bwd_ev[1])
@@ -864,9 +937,8 @@ class _FlatNet(nn.Module):
                 main_s, side_s, e0 = torch.cuda.current_stream(self.device_), self._bwd_side(), self._bwd_ev[0]
                 e0.record(main_s)
             else:
-                call("harl_mlp_dw_partials", ptr(self.dz[cur]), 0, 0, ho, ptr(self.xh[l - 1]), 0, 0, None, None, None, hi, M,
-                     ptr(self.part[po[l]:]), nwg, s, tag="dw_hidden")
-            if l == 1 and fuse_dw1:
+                self._dw_atl(self.dz[cur], ho, self.xh[l - 1], hi, M, l, s, "dw_hidden")
+            if dw1_here:
                 call("harl_mlp_bwd_dx", ptr(self.dz[cur]), ptr(self.xh[0]), ptr(self.rmask[0]), ptr(self.rstd[0]), M, ho, hi,
                      ptr(Wp), None, ptr(self.x0n), self.kp0, ptr(self.part[po[0]:]), nwg, s, tag="bwd_dx_dw1")
             else:
@@ -875,32 +947,27 @@ class _FlatNet(nn.Module):
             if two:
                 side_s.wait_event(e0)
                 with torch.cuda.stream(side_s):
-                    call("harl_mlp_dw_partials", ptr(self.dz[cur]), 0, 0, ho, ptr(self.xh[l - 1]), 0, 0, None, None, None, hi, M,
-                         ptr(self.part[po[l]:]), nwg, side_s.cuda_stream, tag="dw_hidden")
+                    self._dw_atl(self.dz[cur], ho, self.xh[l - 1], hi, M, l, side_s.cuda_stream, "dw_hidden")
                 self._bwd_ev[1].record(side_s)
                 side_pending = True
             cur = 1 - cur
         h0 = self.hidden_sizes[0]
-        use_ln = self.use_feature_normalization
-        if not fuse_dw1:
-            if self.x0n is not None:  # B = normalised inputs as written by the forward pass (ATL, zero-padded to kp0)
-                call("harl_mlp_dw_partials", ptr(self.dz[cur]), 0, 0, h0, ptr(self.x0n), 0, 0, None, None, None, self.kp0, M,
-                     ptr(self.part[po[0]:]), nwg, s, tag="dw_input")
-            else:
-                call("harl_mlp_dw_partials", ptr(self.dz[cur]), 0, 0, h0, ptr(X), 1, X.shape[1], ptr(idx),
-                     ptr(self.mu0) if use_ln else None, ptr(self.rstd0) if use_ln else None, self.in_dim, M,
-                     ptr(self.part[po[0]:]), nwg, s, tag="dw_input")
+        if route.dw1 == "image":  # B = normalised inputs as written by the forward pass (ATL, zero-padded to kp0)
+            self._dw_atl(self.dz[cur], h0, self.x0n, self.kp0, M, 0, s, "dw_input")
+        elif route.dw1 == "rows":
+            use_ln = self.use_feature_normalization
+            call("harl_mlp_dw_partials", ptr(self.dz[cur]), 0, 0, h0, ptr(X), 1, X.shape[1], ptr(idx),
+                 ptr(self.mu0) if use_ln else None, ptr(self.rstd0) if use_ln else None, self.in_dim, M,
+                 ptr(self.part[po[0]:]), nwg, s, tag="dw_input")
         if side_pending:  # the weight gradients enqueued on the second stream
             e1 = self._bwd_ev[1]
             e1.record(self._bwd_side())
             torch.cuda.current_stream(self.device_).wait_event(e1)
-        # deterministic fixed-order combine of every entry's per-workgroup partials, one launch
-        self._combine_partials(s)
 
-    def _backward_trunk_fused(self, M: int, seq: Optional[dict], s) -> None:
+    def _backward_trunk_fused(self, M: int, seq: Optional[dict], s, route: _BwdRoute) -> None:
         """The 64-wide trunk's backward in three launches (csrc/trunk.hip): [the GRU's recurrence, harl_gru_bwd without its
         input side] -> harl_mlp_bwd_trunk (W_ih'^T d gates + every hidden Linear's dx, every dz written once) ->
-        harl_mlp_dw_partials_multi_v (the weight gradients of all MLP layers and of the six gate blocks) -> the combine.
+        harl_mlp_dw_partials_multi_v (the weight gradients of all MLP layers and of the six gate blocks) -> backward_trunk's combine.
         Each stage is the layer kernel's arithmetic; only the first-layer gradient of 33..63-wide inputs differs from the
         layer path in summation order (that path folds it into harl_mlp_bwd_dx on the matrix-pipe transposes)."""
         import ctypes as C
@@ -908,9 +975,7 @@ class _FlatNet(nn.Module):
         spare = [self.dz[2]] if L == 3 else []
         if self.recurrent:
             gp, sv, dg = self.gru_pack, self.rnn_saved, self.rnn_dgate
-            call("harl_gru_bwd", ptr(self.dz[0]), ptr(seq["mask_rows"]), ptr(gp["Wih"]), ptr(gp["Whh"]), ptr(sv[0]),
-                 ptr(sv[1]), ptr(sv[2]), ptr(sv[3]), ptr(sv[4]), 64, seq["L"], seq["m_pad"], ptr(self.xh[-1]),
-                 ptr(self.rmask[-1]), ptr(self.rstd[-1]), ptr(dg[0]), ptr(dg[1]), ptr(dg[2]), ptr(dg[3]), None, s, tag="gru_bwd")
+            self._gru_bwd(seq, None, s)
             dzs = [self.dz[1], self.dz[0]] + spare  # dz of layers L-1 .. 0 (d(loss)/d(h) in dz[0] is dead after the recurrence)
         else:
             dzs = [self.dz[0], self.dz[1]] + spare
@@ -922,8 +987,8 @@ class _FlatNet(nn.Module):
 
             def add(aa, bb, l, k, t, n):
                 a.append(aa), b.append(bb), part.append(self.part[po[l]:]), K.append(k), t0.append(t), nt.append(n)
-            if self.recurrent:  # W_ih' blocks d gi_g^T x_hat_mlp (g = r, z, n), W_hh blocks d gh_g^T h~ (dhn for n)
-                for k, (aa, bb) in enumerate(zip((dg[0], dg[1], dg[2], dg[0], dg[1], dg[3]), [self.xh[-1]] * 3 + [sv[0]] * 3)):
+            if self.recurrent:
+                for k, (aa, bb) in enumerate(zip(*self._gate_operands(0))):
                     add(aa, bb, L + k, 64, 0, 2)
             for j, l in enumerate(range(L - 1, 0, -1)):
                 add(dzs[j], self.xh[l - 1], l, 64, 0, 2)
@@ -945,7 +1010,7 @@ class _FlatNet(nn.Module):
         # opt-in: 26.4 / 25.9 against 23.8 / 23.7 ms per SMAC 3s5z update, 116.1 / 116.3 against 114.0 / 114.1 ms at 4096
         # threads (gpurun_out/r06h, call 3) -- two cross-stream dependencies per optimiser step cost more than the ~40 us of
         # overlap return.  Default: one launch for all nine problems behind the trunk's backward.
-        two = (self.recurrent and self.device_.type == "cuda" and os.environ.get("HARL_TRUNK_DW_STREAM", "0") == "1")
+        two = route.gates_side
         if two:
             main_s, side_s, (e0, e1) = torch.cuda.current_stream(self.device_), self._bwd_side(), self._bwd_ev
             e0.record(main_s)
@@ -963,9 +1028,8 @@ class _FlatNet(nn.Module):
         # per row on a launch that is bound by its row traffic), then the MLP layers.  Bit-identical to the nine problems of the
         # generic launch; it is one launch more, which costs what it saves at 81 920 rows per minibatch (24.2 / 24.3 against
         # 23.8 / 24.1 ms per SMAC 3s5z update) and pays at 655 360 (112.2 / 112.6 against 116.7 / 116.7 ms; gpurun_out/r06h call
-        # 6): taken from 160 000 rows.  HARL_GRU_DW6=1 / 0 force it on / off.
-        g6 = os.environ.get("HARL_GRU_DW6", "auto")
-        gru6 = self.recurrent and not two and (g6 == "1" or (g6 == "auto" and M >= 160000))
+        # 6): taken from 160 000 rows (_backward_route).
+        gru6 = route.gates_dw6
         if gru6:
             call("harl_gru_dw6", ptr(dg[0]), ptr(dg[1]), ptr(dg[2]), ptr(dg[3]), ptr(self.xh[-1]), ptr(sv[0]), dw_gates[3], M, nwg, s,
                  tag="dw_gru")
@@ -973,7 +1037,6 @@ class _FlatNet(nn.Module):
         call("harl_mlp_dw_partials_multi_v", dw[0], *dw[1:4], 64, *dw[4:], M, nwg, s, tag="dw_trunk")
         if two:
             main_s.wait_event(e1)
-        self._combine_partials(s)
 
     # ---- grouped heads (MultiDiscrete: csrc/multihead.hip, Categorical of 65..512 actions: csrc/cathead.hip): logits of every
     # group from the head input; backward of the groups
@@ -1002,11 +1065,9 @@ class _FlatNet(nn.Module):
         d(loss)/d(head input) in self.dz[0]: the layer kernels of a hidden Linear (sum over the groups)."""
         fx, fmask, frstd, fh = self.feat()
         s = stream()
-        nh = len(self._md_sp)
-        po = self._part_offs[-nh:]
+        nh = len(self._md_sp)  # (the groups are the last nh table entries)
         for g, ((Wp, _), dzg, sp) in enumerate(zip(self._head_packs, self.md_z, self._md_sp)):
-            call("harl_mlp_dw_partials", ptr(dzg), 0, 0, sp, ptr(fx), 0, 0, None, None, None, fh, M,
-                 ptr(self.part[po[g]:]), self.n_wg, s, tag="dw_head")
+            self._dw_atl(dzg, sp, fx, fh, M, g - nh, s, "dw_head")
             call("harl_mlp_bwd_dx", ptr(dzg), ptr(fx), ptr(fmask), ptr(frstd), M, sp, fh, ptr(Wp),
                  ptr(self.dz[0 if g == 0 else 1]), None, 0, None, 0, s, tag="bwd_dx")
             if g > 0:

@@ -446,6 +446,15 @@ def test_gate_weight_gradients_as_one_problem_bit_identical(i, monkeypatch):
     _assert_all(g.check_trunk_fused(g.TRUNK_SPECS[i]))
 
 
+def test_gate_weight_gradients_on_a_second_stream_bit_identical(monkeypatch):
+    """HARL_TRUNK_DW_STREAM=1 (opt-in: the six gate problems of harl_mlp_dw_partials_multi_v on a second stream next to
+    harl_mlp_bwd_trunk, the MLP's problems behind it on the main one; no partial block is shared) inside the one-launch trunk path
+    against the layer launches: the same bits."""
+    monkeypatch.setenv("HARL_TRUNK_DW_STREAM", "1")
+    g = _G()
+    _assert_all(g.check_trunk_fused(g.TRUNK_SPECS[1]))
+
+
 @pytest.mark.parametrize("first", [True, False])
 @pytest.mark.parametrize("M", [45, 300, 32 * 4 * 7 + 1, 32 * 4 * 256 * 3 + 32 * 5 + 9])
 def test_whole_layer_backward_in_one_launch(M, first):

@@ -1,7 +1,9 @@
 """The first-layer launch route of a network (nets._FlatNet._first_launch) and what it does with the normalised-input image,
 host side without a GPU (C-ABI calls recorded instead of executed): the launch traces of whole train() calls against the ones
 recorded before the route was decided in one place (tests/golden/launch_traces.json, tools/launch_trace.py), and the image
-contract between prepare_x0n / x0n_multi_item and the forward that follows them."""
+contract between prepare_x0n / x0n_multi_item and the forward that follows them.  The recorded matrix also holds the routes of
+the backward (nets._FlatNet._backward_route; configurations 15 and up were recorded before that one was decided in one place):
+BACKWARD_REACHES names what each configuration must go on launching."""
 import importlib.util
 import json
 import os
@@ -45,6 +47,55 @@ def test_launch_traces_equal_the_recorded_ones(stub_kernels, monkeypatch):  # no
     assert {a[2] for a in asked} == {True, False} and {a[3] for a in asked} == {True, False}
     assert {a[:2] for a in asked} == {("act", "cached"), ("panel", "cached"), ("trunk", "cached"), ("wide", "cached"),
                                       ("fused2x", "cached_identity"), ("fused2", "clobbers"), ("input", "clobbers")}
+    # ... and every route of the backward (nets._backward_route): each configuration recorded for one still launches it
+    for name, reaches in BACKWARD_REACHES.items():
+        for r in reaches:
+            entry_tag, pred = (r, None) if isinstance(r, str) else r
+            hits = _launches(got[name], entry_tag)
+            assert hits and (pred is None or any(pred(a) for a in hits)), (name, entry_tag)
+    assert not _launches(got["16_h128x2_obs40_bwd_fused"], "harl_mlp_bwd_dx_dw:bwd_full")       # 64-wide image: the layer kernels
+    assert not _launches(got["16_h128x2_obs40_bwd_fused"], "harl_mlp_bwd_dx_dw:bwd_full_dw1")
+    assert not _launches(got["22_gru64_dw6"], "harl_mlp_dw_partials_multi:dw_gru")
+    t24 = got["24_gru64_n2"]  # two GRU layers: two gate-gradient launches per backward
+    assert len(_launches(t24, "harl_mlp_dw_partials_multi:dw_gru")) == 2 * len(_launches(t24, "harl_mlp_dw_partials:dw_input"))
+    one_layer = {c[0] for c in got["32_h128_obs40_1layer"]}  # L = 1: no hidden layer to go back through
+    assert not one_layer & {"harl_mlp_bwd_dx", "harl_mlp_bwd_dx_dw", "harl_mlp_bwd_trunk"}
+    assert not _launches(got["32_h128_obs40_1layer"], "harl_mlp_dw_partials:dw_hidden")
+
+
+def _launches(trace, entry_tag):
+    """Argument lists of the calls ``entry:tag`` of a full trace."""
+    return [c[2] for c in trace if f"{c[0]}:{c[1] or ''}" == entry_tag]
+
+
+# configuration -> the launches its backward was recorded to reach: "entry:tag", or ("entry:tag", predicate on the arguments
+# of one such call).  Argument positions as in include/harl_hip.h: harl_mlp_bwd_dx_dw(.., dz_prev [8], x0n [9], .., fill [14]),
+# harl_gru_bwd(.., dx [19]), harl_mlp_dw_partials(A, a_rows [1], lda, HO [3], B, b_rows [5], ldb [6], ..)
+BACKWARD_REACHES = {
+    "15_h128x3_bwd_fused": [("harl_mlp_bwd_dx_dw:bwd_full", lambda a: a[8] is not None and a[9] is None),
+                            ("harl_mlp_bwd_dx_dw:bwd_full_dw1", lambda a: a[8] is None and a[10] == 32)],
+    "16_h128x2_obs40_bwd_fused": [("harl_mlp_bwd_dx:bwd_dx_dw1", lambda a: a[10] == 64), "harl_mlp_dw_partials:dw_hidden"],
+    "17_h128x2_obs40_bwd_k64": [("harl_mlp_bwd_dx_dw:bwd_full", lambda a: a[8] is not None and a[6] == 128),  # writes dz_1
+                                ("harl_mlp_dw_partials:dw_input", lambda a: a[10] == 64)],
+    "18_h128x2_nofill": [("harl_mlp_bwd_dx_dw:bwd_full_dw1", lambda a: a[14] == 0)],
+    "19_h128x2_fill": [("harl_mlp_bwd_dx_dw:bwd_full_dw1", lambda a: a[14] == 2)],
+    "14b_h128x2_bwd_fused": [("harl_mlp_bwd_dx_dw:bwd_full_dw1", lambda a: a[14] == 1)],
+    "20_h128x2_fused1": ["harl_update_bwd:update_bwd"],
+    "21_gru64_layers": [("harl_gru_bwd:gru_bwd", lambda a: a[19] is not None and a[9] == 64), "harl_mlp_dw_partials_multi:dw_gru",
+                        "harl_mlp_dw_partials:dw_input"],
+    "22_gru64_dw6": ["harl_gru_dw6:dw_gru", ("harl_gru_bwd:gru_bwd", lambda a: a[19] is None),
+                     ("harl_mlp_dw_partials_multi_v:dw_trunk", lambda a: a[0] == 2)],  # the MLP's problems only
+    "12_h64x2_obs128_gru": [("harl_mlp_dw_partials_multi_v:dw_trunk", lambda a: a[0] == 8)],  # ... with the six gate blocks
+    "23_gru128": ["harl_gru_cell_bwd:gru_cell_bwd", "harl_mlp_dw_partials_multi:dw_gru", ("harl_mlp_bwd_dx:bwd_dx_dw1", lambda a: a[5] == 128)],
+    "24_gru64_n2": ["harl_mlp_linear:gru_gi_bwd", "harl_gru_cell_bwd:gru_cell_bwd", "harl_mlp_dw_partials_multi:dw_gru"],
+    "25_disc50": [("harl_mlp_dw_partials:dw_head", lambda a: a[1] == 0 and a[3] == 64)],  # the ATL(64) image of dhead
+    "26_obs520": [("harl_mlp_dw_partials:dw_input", lambda a: a[5] == 1 and a[6] == 520)],  # B = the gathered rows
+    "27_h64x3_obs128": [("harl_mlp_bwd_trunk:bwd_trunk", lambda a: a[2] == 2 and a[12][2].endswith(".dz[2]+0"))],  # the spare dz buffer
+    "31_mappo_gru": ["harl_gru_bwd:gru_bwd", "harl_mlp_bwd_trunk:bwd_trunk", "harl_mlp_dw_partials_multi_v:dw_trunk"],
+    "32_h128_obs40_1layer": [("harl_mlp_dw_partials:dw_input", lambda a: a[10] == 32)],
+    "10_h256x2": ["harl_mlp_panel_bwd:bwd_panel"],
+    "11_h128x2_tanh": ["harl_act_bwd:act_bwd"],
+}
 
 
 def _cases(monkeypatch):

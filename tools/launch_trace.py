@@ -7,7 +7,7 @@ of the Python orchestration that hands another workspace to a kernel, or stops d
 trace, while addresses and the allocator's reuse of them do not.
 
     python tools/launch_trace.py --check tests/golden/launch_traces.json   # regenerate and compare (exit status 1: differs)
-    python tools/launch_trace.py --write tests/golden/launch_traces.json   # per configuration: names + tags, SHA-256 of the rest
+    python tools/launch_trace.py --write tests/golden/launch_traces.json   # per configuration: names + tags, SHA-256 of the rest (extends FIXTURE's name table)
     python tools/launch_trace.py --full a.json                             # the full traces (about 400 KB)
     python tools/launch_trace.py --diff a.json b.json                      # first differing call of two --full dumps
 
@@ -27,6 +27,7 @@ import torch  # noqa: E402
 
 MODS = ("nets", "buffers", "happo", "hatrpo", "mappo", "v_critic", "valuenorm", "runner", "gru_wide")
 _SMAC = dict(obs=128, sobs=128)
+_GRU = dict(_SMAC, use_recurrent_policy=True, data_chunk_length=4)
 # name -> (hidden sizes, runner keywords, environment).  Between them: every first-layer launch of nets.forward_trunk, with
 # and without a row-index tensor (one / two minibatches), whole trunks and trunks that stop in front of harl_update_last_*.
 CONFIGS = {
@@ -45,6 +46,22 @@ CONFIGS = {
     "13_h128x2_discrete100": ([128, 128], dict(discrete=100), {}),
     "14a_h128x2_logp": ([128, 128], {}, dict(HARL_FUSED_UPDATE="logp")),
     "14b_h128x2_bwd_fused": ([128, 128], {}, dict(HARL_BWD_FUSED="1")),
+    # ... and the routes of nets.backward_trunk the fifteen above do not reach (what each launches: tests/test_launch_trace_cpu.py)
+    "15_h128x3_bwd_fused": ([128, 128, 128], {}, dict(HARL_BWD_FUSED="1")),
+    "16_h128x2_obs40_bwd_fused": ([128, 128], dict(obs=40, sobs=60), dict(HARL_BWD_FUSED="1")),
+    "17_h128x2_obs40_bwd_k64": ([128, 128], dict(obs=40, sobs=60), dict(HARL_BWD_FUSED="1", HARL_BWD_K64="1")),
+    "18_h128x2_nofill": ([128, 128], {}, dict(HARL_BWD_FUSED="nofill")),
+    "19_h128x2_fill": ([128, 128], {}, dict(HARL_BWD_FUSED="fill")),
+    "20_h128x2_fused1": ([128, 128], {}, dict(HARL_FUSED_UPDATE="1")),
+    "21_gru64_layers": ([64, 64], dict(_GRU), dict(HARL_TRUNK_FUSED="0")),
+    "22_gru64_dw6": ([64, 64], dict(_GRU), dict(HARL_GRU_DW6="1")),
+    "23_gru128": ([128, 128], dict(use_recurrent_policy=True, data_chunk_length=4), {}),
+    "24_gru64_n2": ([64, 64], dict(_GRU, recurrent_n=2), {}),
+    "25_disc50": ([128, 128], dict(discrete=50), {}),
+    "26_obs520": ([128, 128], dict(obs=520, sobs=520), {}),
+    "27_h64x3_obs128": ([64, 64, 64], dict(_SMAC), {}),
+    "31_mappo_gru": ([64, 64], dict(_GRU, algo="mappo"), {}),
+    "32_h128_obs40_1layer": ([128], dict(obs=40), {}),
 }
 # the switches a configuration may set: cleared around every run, so that the caller's environment does not leak into a trace
 SWITCHES = ("HARL_FUSED_UPDATE", "HARL_BWD_FUSED", "HARL_BWD_K64", "HARL_TRUNK_FUSED", "HARL_GRAPH", "HARL_BWD_STREAMS",
@@ -52,8 +69,8 @@ SWITCHES = ("HARL_FUSED_UPDATE", "HARL_BWD_FUSED", "HARL_BWD_K64", "HARL_TRUNK_F
             "HARL_GRU_DW6", "HARL_TRUNK_DW_STREAM", "HARL_LIB")
 
 
-def make_runner(hidden, obs=19, sobs=11, act=3, discrete=0, T=8, N=8, A=2, **over):
-    """tests/test_hybrid_cpu._runner, plus a Discrete(``discrete``) action space."""
+def make_runner(hidden, obs=19, sobs=11, act=3, discrete=0, T=8, N=8, A=2, algo="happo", **over):
+    """tests/test_hybrid_cpu._runner, plus a Discrete(``discrete``) action space and the runner of ``algo``."""
     from harl_amd.runner import RUNNER_REGISTRY
     from harl_amd.synthetic import Shapes, make_buffers
     from tests.gpu_checks import Box, Discrete, default_args
@@ -62,7 +79,7 @@ def make_runner(hidden, obs=19, sobs=11, act=3, discrete=0, T=8, N=8, A=2, **ove
                  use_proper_time_limits=True, model_dir=None, eval_interval=25, use_eval=False, log_interval=1,
                  num_env_steps=T * N * 2)
     space = Discrete(discrete) if discrete else Box((act,))
-    r = RUNNER_REGISTRY["happo"](dict(algo="happo"), dict(train=train, model=dict(a), algo=dict(a)), dict(state_type="EP"),
+    r = RUNNER_REGISTRY[algo](dict(algo=algo), dict(train=train, model=dict(a), algo=dict(a)), dict(state_type="EP"),
                                  obs_spaces=[Box((obs,))] * A, share_obs_space=Box((sobs,)), act_spaces=[space] * A,
                                  device=torch.device("cpu"))
     sh = Shapes(T=T, N=N, A=A, obs_dim=obs, share_obs_dim=sobs, act_dim=discrete or act, discrete=bool(discrete),
@@ -169,10 +186,12 @@ def digest(trace):
     return hashlib.sha256(json.dumps(trace, separators=(",", ":")).encode()).hexdigest()
 
 
-def summarise(traces):
+def summarise(traces, keep=()):
     """What the committed fixture keeps of the full traces (they are several hundred KB): per configuration every call's entry
-    point and tag in order -- as indices into ONE table of "entry:tag" names -- and a SHA-256 of the full trace."""
-    names = sorted({f"{c[0]}:{c[1] or ''}" for t in traces.values() for c in t})
+    point and tag in order -- as indices into ONE table of "entry:tag" names -- and a SHA-256 of the full trace.  ``keep``: the
+    name table of the fixture that is being extended; its names keep their indices (and the recorded lines their bytes), new
+    names follow."""
+    names = list(keep) + sorted({f"{c[0]}:{c[1] or ''}" for t in traces.values() for c in t} - set(keep))
     at = {n: i for i, n in enumerate(names)}
     return dict(names=names, traces={k: dict(calls=[at[f"{c[0]}:{c[1] or ''}"] for c in t], sha256=digest(t))
                                      for k, t in traces.items()})
@@ -244,7 +263,11 @@ def main():
             with open(a.full, "w") as f:
                 json.dump(traces, f, separators=(",", ":"))
         elif a.write:
-            fx = summarise(traces)
+            keep = ()
+            if os.path.exists(a.write):
+                with open(a.write) as f:
+                    keep = json.load(f)["names"]
+            fx = summarise(traces, keep)
             with open(a.write, "w") as f:  # one configuration per line
                 f.write('{"names": ' + json.dumps(fx["names"]) + ',\n "traces": {\n' + ",\n".join(
                     f'  {json.dumps(k)}: {json.dumps(t, separators=(",", ":"))}' for k, t in fx["traces"].items()) + "\n}}\n")
