@@ -82,30 +82,14 @@ class OnPolicyBase:
         resets.  Returns the final hidden state [m, H] when ``h_last`` is set."""
         net = self.actor
         agg = int(self.action_aggregation == "mean")
-        if net.grouped and not net.recurrent:  # MultiDiscrete / wide Categorical: trunk -> logits of every group -> log-softmax
-            if not reuse_trunk:
-                net.forward_trunk(obs, None, M, for_backward=False)
-            net.md_logits(M)
-            if net.cat_wide:
-                call("harl_cat_head_logp", *net.cat_layout(), M, None, ptr(actions), ptr(avail), ptr(logp_out), None,
-                     ptr(old_logp), ptr(factor), ptr(head_out), 0, 0, stream(), tag="cat_head_logp")
-                return None
-            call("harl_md_head_logp", *net.md_layout(), M, ptr(actions), ptr(logp_out), ptr(old_logp),
-                 0 if old_logp is None else old_logp.shape[1], ptr(factor), agg, ptr(head_out), 0, 0, stream(),
-                 tag="md_head_logp")
-            return None
         if not reuse_trunk and net.fused_update_ok(None, train=False):  # forward + head in one launch, x_hat_2 never leaves the chip
-            call("harl_update_logp", *net.fused_args(obs, M), ptr(net.log_std()), net.std_x_coef, net.std_y_coef,
-                 int(net.discrete), net.act_dim, ptr(actions), ptr(avail), ptr(logp_out), ptr(old_logp), ptr(factor), agg,
-                 ptr(head_out), stream(), tag="update_logp")
+            call("harl_update_logp", *net.fused_args(obs, M), *net.dist_args(), ptr(actions), ptr(avail), ptr(logp_out),
+                 ptr(old_logp), ptr(factor), agg, ptr(head_out), stream(), tag="update_logp")
             return None
         if not net.recurrent:
             if not reuse_trunk:  # reuse_trunk: x_hat_L of these rows under the current weights is still in the workspace
                 net.forward_trunk(obs, None, M, for_backward=False)
-            Wp, bp = net._packs[-1]
-            call("harl_actor_head_logp", ptr(net.xh[-1]), M, net.hidden_sizes[-1], ptr(Wp), ptr(bp), ptr(net.log_std()),
-                 net.std_x_coef, net.std_y_coef, int(net.discrete), net.act_dim, ptr(actions), ptr(avail), ptr(logp_out),
-                 ptr(old_logp), ptr(factor), agg, ptr(head_out), 0, 0, stream(), tag="actor_head_logp")
+            net.head_logp(M, actions, avail, logp_out, old_logp, factor, head_out, agg)
             return None
         H = net.hidden_sizes[-1]
         m = rnn_states.shape[0]
@@ -120,21 +104,7 @@ class OnPolicyBase:
         a_p, av_p, old_p, f_p = g(actions), g(avail), g(old_logp), g(factor)
         lo_p, ho_p = tmp(logp_out), tmp(head_out)
         net.forward_trunk(obs, idx, Mp, for_backward=False, seq=seq)
-        fx, _, _, fh = net.feat()
-        Wp, bp = net._packs[-1]
-        if net.cat_wide:
-            net.md_logits(Mp)
-            call("harl_cat_head_logp", *net.cat_layout(), Mp, None, ptr(a_p), ptr(av_p), ptr(lo_p), None, ptr(old_p), ptr(f_p),
-                 ptr(ho_p), m, seq["m_pad"], stream(), tag="cat_head_logp")
-        elif net.md:
-            net.md_logits(Mp)
-            call("harl_md_head_logp", *net.md_layout(), Mp, ptr(a_p), ptr(lo_p), ptr(old_p),
-                 0 if old_p is None else old_p.shape[1], ptr(f_p), agg, ptr(ho_p), m, seq["m_pad"], stream(),
-                 tag="md_head_logp")
-        else:
-            call("harl_actor_head_logp", ptr(fx), Mp, fh, ptr(Wp), ptr(bp), ptr(net.log_std()), net.std_x_coef,
-                 net.std_y_coef, int(net.discrete), net.act_dim, ptr(a_p), ptr(av_p), ptr(lo_p), ptr(old_p), ptr(f_p), agg,
-                 ptr(ho_p), m, seq["m_pad"], stream(), tag="actor_head_logp")
+        net.head_logp(Mp, a_p, av_p, lo_p, old_p, f_p, ho_p, agg, m, seq["m_pad"])
         if padded:
             for dst, src in ((logp_out, lo_p), (head_out, ho_p), (factor, f_p)):
                 if dst is not None:
@@ -150,10 +120,10 @@ class OnPolicyBase:
             for n in net.nvec:
                 off.append(off[-1] + int(n))
             self._head_off = torch.tensor(off, dtype=torch.int32, device=self.device)
-        call("harl_dist_rows", ptr(head), M, net.act_dim, int(net.discrete), None if net.discrete else ptr(net.log_std()),
-             net.std_x_coef, net.std_y_coef, ptr(noise), ptr(actions), ptr(self._head_off) if net.md else None,
-             len(net.nvec) if net.md else 1, 1, ptr(logp), ptr(probs), ptr(argmax_out), ptr(ent_rows), ptr(sigma_out), stream(),
-             tag="dist_rows")
+        log_std, xc, yc, discrete, act_dim = net.dist_args()
+        call("harl_dist_rows", ptr(head), M, act_dim, discrete, log_std, xc, yc, ptr(noise), ptr(actions),
+             ptr(self._head_off) if net.md else None, len(net.nvec) if net.md else 1, 1, ptr(logp), ptr(probs), ptr(argmax_out),
+             ptr(ent_rows), ptr(sigma_out), stream(), tag="dist_rows")
 
     def evaluate_actions(self, obs, rnn_states_actor, action, masks, available_actions=None, active_masks=None):
         """(action_log_probs [B, act_w], dist_entropy 0-d, action_distribution) as the reference returns them
@@ -194,7 +164,7 @@ class OnPolicyBase:
     @torch.no_grad()
     def get_actions(self, obs, rnn_states_actor, masks, available_actions=None, deterministic=False):
         """Rollout-side sampling (on_policy_base.py:52-69 -> StochasticPolicy.forward, act.py:45-86).  The trunk, GRU
-        step and head run on the HIP kernels (head outputs via ``harl_actor_head_logp(head_out=...)``); the draw itself
+        step and head run on the HIP kernels (head outputs via ``StochasticPolicy.head_logp(head_out=...)``); the draw itself
         uses torch's device generator, which is what the reference's ``Normal.sample()/Categorical.sample()`` use on a
         GPU.  Returns device tensors (actions [B, act_w], action_log_probs [B, act_w], rnn_states [B, 1, H])."""
         net = self.actor
@@ -261,7 +231,7 @@ class HAPPO(OnPolicyBase):
         self.entropy_coef = args["entropy_coef"]
         self.use_max_grad_norm = args["use_max_grad_norm"]
         self.max_grad_norm = args["max_grad_norm"]
-        self._surrogate_mode = 0  # harl_actor_head_loss `trpo` argument: 0 = clipped (HAPPO)
+        self._surrogate_mode = 0  # the loss launches' mode (StochasticPolicy.head_loss): 0 = clipped (HAPPO)
         self._info = torch.zeros(4, dtype=torch.float64, device=self.device)  # fp64 sums of the per-update fp32 policy_loss, dist_entropy, grad_norm, ratio (the reference sums .item() values: happo.py:145-150)
         self._grad_tap = None
         self._trace = None  # test hook: list receiving a clone of the running statistics after every optimiser step
@@ -286,13 +256,13 @@ class HAPPO(OnPolicyBase):
         pre-step parameters (by batch position).  ``factor`` None = 1 (MAPPO)."""
         net = self.actor
         s = stream()
+        # clip, entropy coefficient, aggregation, surrogate mode: the same four in every loss launch
+        loss = (float(self.clip_param), float(self.entropy_coef), int(self.action_aggregation == "mean"), self._surrogate_mode)
         if net.fused_update_ok(idx, seq):  # fused forward + loss (csrc/update.hip), then the layer backward (hybrid) or harl_update_bwd
             fa = net.fused_args(obs, m)
             self._await_factor()
-            call("harl_update_fwd_actor", *fa, ptr(net.log_std()), net.std_x_coef, net.std_y_coef, int(net.discrete),
-                 net.act_dim, ptr(actions), ptr(avail), ptr(old_logp), ptr(adv), ptr(adv_moments), ptr(factor),
-                 ptr(active), float(self.clip_param), float(self.entropy_coef), int(self.action_aggregation == "mean"),
-                 self._surrogate_mode, ptr(logp_out), ptr(net.dz[0]), ptr(net.part_scalars),
+            call("harl_update_fwd_actor", *fa, *net.dist_args(), ptr(actions), ptr(avail), ptr(old_logp), ptr(adv),
+                 ptr(adv_moments), ptr(factor), ptr(active), *loss, ptr(logp_out), ptr(net.dz[0]), ptr(net.part_scalars),
                  ptr(net.part[net._part_offs[-1]:]), net.n_wg, *net.hybrid_outputs(), s, tag="update_fwd")
             net.backward_after_fused(obs, m)
             return net.n_wg
@@ -302,44 +272,18 @@ class HAPPO(OnPolicyBase):
             (Wl, bl), (Wh, bh) = net._packs[L - 1], net._packs[-1]
             self._await_factor()
             call("harl_update_last_actor", ptr(net.xh[L - 2]), m, net.hidden_sizes[-1], ptr(Wl), ptr(bl), ptr(Wh), ptr(bh),
-                 ptr(net.log_std()), net.std_x_coef, net.std_y_coef, int(net.discrete), net.act_dim, ptr(idx), ptr(actions),
-                 ptr(avail), ptr(old_logp), ptr(adv), ptr(adv_moments), ptr(factor), ptr(active), float(self.clip_param),
-                 float(self.entropy_coef), int(self.action_aggregation == "mean"), self._surrogate_mode, ptr(logp_out),
-                 ptr(net.dz[0]), ptr(net.part_scalars), ptr(net.part[net._part_offs[-1]:]), net.n_wg, s, tag="update_last")
+                 *net.dist_args(), ptr(idx), ptr(actions), ptr(avail), ptr(old_logp), ptr(adv), ptr(adv_moments), ptr(factor),
+                 ptr(active), *loss, ptr(logp_out), ptr(net.dz[0]), ptr(net.part_scalars), ptr(net.part[net._part_offs[-1]:]),
+                 net.n_wg, s, tag="update_last")
             net.backward_trunk(obs, idx, m, head_dw_done=True)
             return net.n_wg
         net.forward_trunk(obs, idx, m, seq=seq)
-        Wp, bp = net._packs[-1]
-        fx, fmask, frstd, fh = net.feat()
         mv, mp = (seq["m"], seq["m_pad"]) if seq is not None else (0, 0)
         self._await_factor()
-        if net.cat_wide:  # Categorical of 65..512 actions (csrc/cathead.hip): as MultiDiscrete below, ONE softmax over the groups
-            net.md_logits(m)
-            nblk = _lib.load().harl_head_blocks(m)
-            call("harl_cat_head_loss", *net.cat_layout(), m, ptr(idx), ptr(actions), ptr(avail), ptr(old_logp), ptr(adv),
-                 ptr(adv_moments), ptr(factor), ptr(active), float(self.clip_param), float(self.entropy_coef),
-                 self._surrogate_mode, mv, mp, ptr(logp_out), ptr(net.part_scalars), nblk, s, tag="cat_head_loss")
-            net.backward_trunk(obs, idx, m, seq=seq)
-            return nblk
-        if net.md:  # MultiDiscrete (csrc/multihead.hip): logits GEMM, per-sample loss -> d(logits) in place, layer-kernel backward
-            net.md_logits(m)
-            nblk = _lib.load().harl_head_blocks(m)
-            lay = net.md_layout()
-            call("harl_md_head_loss", lay[0], *lay, m, ptr(idx), ptr(actions), ptr(old_logp), old_logp.shape[1], ptr(adv),
-                 ptr(adv_moments), ptr(factor), ptr(active), ptr(self._md_ent_scale(idx, m, active, seq)),
-                 float(self.clip_param), float(self.entropy_coef), int(self.action_aggregation == "mean"),
-                 self._surrogate_mode, mv, mp, ptr(logp_out), ptr(net.part_scalars), nblk, s, tag="md_head_loss")
-            net.backward_trunk(obs, idx, m, seq=seq)
-            return nblk
-        call("harl_actor_head_loss", ptr(fx), ptr(fmask), ptr(frstd), m, fh,
-             ptr(Wp), ptr(bp), ptr(net.log_std()), net.std_x_coef, net.std_y_coef, int(net.discrete), net.act_dim,
-             ptr(idx), ptr(actions), ptr(avail), ptr(old_logp), ptr(adv), ptr(adv_moments), ptr(factor), ptr(active),
-             float(self.clip_param), float(self.entropy_coef), int(self.action_aggregation == "mean"), self._surrogate_mode,
-             mv, mp, ptr(logp_out), ptr(net.dz[0]), ptr(net.dhead), ptr(net.part_scalars),
-             None if net.wide_head else ptr(net.part[net._part_offs[-1]:]), net.n_wg, s,
-             tag="actor_head_loss")  # head dW fused into this launch (heads of 33..64 actions: separate dW pass)
-        net.backward_trunk(obs, idx, m, seq=seq, head_dw_done=not net.wide_head)
-        return net.n_wg if not net.wide_head else _lib.load().harl_head_blocks(m)  # rows of part_scalars
+        nblk, head_dw_done = net.head_loss(m, idx, actions, avail, old_logp, adv, adv_moments, factor, active, *loss, mv, mp,
+                                           logp_out, md_ent_scale=lambda: self._md_ent_scale(idx, m, active, seq))
+        net.backward_trunk(obs, idx, m, seq=seq, head_dw_done=head_dw_done)
+        return nblk  # rows of part_scalars
 
     def _md_ent_scale(self, idx, m, active, seq) -> Optional[torch.Tensor]:
         """MultiDiscrete: device scalar sum(active) / rows of the (global) minibatch.  The reference's entropy bonus there is
@@ -442,23 +386,17 @@ class HAPPO(OnPolicyBase):
         m = obs.shape[0]
         before = self._info.clone()
         self.actor.fold()
+        seq, idx, rows = None, None, m
         if self.actor.recurrent:  # gathered [L*m, .] l-major minibatch + rnn_states [m, 1, H] (recurrent generators)
             HS = self.actor.hidden_sizes[-1] * self.actor.recurrent_n
             nseq = _as_dev(_rnn, dev).shape[0]
             seq = build_seq(dev, m // nseq, nseq, HS, h0=_as_dev(_rnn, dev).reshape(nseq, HS), masks_src=_as_dev(_masks, dev))
-            idx = seq["idx"]
-            self._update_core(obs.reshape(m, -1), idx, seq["L"] * seq["m_pad"], _as_dev(actions, dev).reshape(m, -1),
-                              None if avail is None else _as_dev(avail, dev).reshape(m, -1),
-                              _as_dev(old_logp, dev).reshape(m, -1), _as_dev(adv, dev).reshape(m), None,
-                              None if factor is None else _as_dev(factor, dev).reshape(m),
-                              _as_dev(active, dev).reshape(m) if self.use_policy_active_masks else None, seq=seq)
-            d = self._info - before
-            return d[0], d[1], d[2], d[3]
-        self._update_core(obs.reshape(m, -1), None, m, _as_dev(actions, dev).reshape(m, -1),
+            idx, rows = seq["idx"], seq["L"] * seq["m_pad"]
+        self._update_core(obs.reshape(m, -1), idx, rows, _as_dev(actions, dev).reshape(m, -1),
                           None if avail is None else _as_dev(avail, dev).reshape(m, -1),
                           _as_dev(old_logp, dev).reshape(m, -1), _as_dev(adv, dev).reshape(m), None,
                           None if factor is None else _as_dev(factor, dev).reshape(m),
-                          _as_dev(active, dev).reshape(m) if self.use_policy_active_masks else None)
+                          _as_dev(active, dev).reshape(m) if self.use_policy_active_masks else None, seq=seq)
         d = self._info - before
         return d[0], d[1], d[2], d[3]
 

@@ -55,21 +55,12 @@ class HATRPO(OnPolicyBase):
         net = self.actor
         idx = None if seq is None else seq["idx"]
         net.forward_trunk(obs, idx, m, for_backward=True, seq=seq)
-        Wp, bp = net._packs[-1]
         s = stream()
-        fx, fmask, frstd, fh = net.feat()
         mv, mp = (seq["m"], seq["m_pad"]) if seq is not None else (0, 0)
-        if net.cat_wide:  # Categorical of 65..512 actions (csrc/cathead.hip): logits of every group, the loss in HATRPO's form (mode 1)
-            net.md_logits(m)
-            call("harl_cat_head_loss", *net.cat_layout(), m, ptr(idx), ptr(actions), ptr(avail), ptr(old_logp), ptr(adv),
-                 ptr(adv_moments), ptr(factor), ptr(active), 0.0, 0.0, 1, mv, mp, None, ptr(net.part_scalars),
-                 _lib.load().harl_head_blocks(m), s, tag="cat_head_loss")
-        else:
-            call("harl_actor_head_loss", ptr(fx), ptr(fmask), ptr(frstd), m, fh,
-                 ptr(Wp), ptr(bp), ptr(net.log_std()), net.std_x_coef, net.std_y_coef, int(net.discrete), net.act_dim,
-                 ptr(idx), ptr(actions), ptr(avail), ptr(old_logp), ptr(adv), ptr(adv_moments), ptr(factor), ptr(active),
-                 0.0, 0.0, int(self.action_aggregation == "mean"), 1, mv, mp, None, ptr(net.dz[0]), ptr(net.dhead), ptr(net.part_scalars), None, 0, s)
-        call("harl_reduce_scalars_set", ptr(net.part_scalars), _lib.load().harl_head_blocks(m), ptr(net.scalars), s)
+        # the loss in HATRPO's form: mode 1, no clip, no entropy coefficient, the head's weight gradient left to backward_trunk
+        nblk, _ = net.head_loss(m, idx, actions, avail, old_logp, adv, adv_moments, factor, active, 0.0, 0.0,
+                                int(self.action_aggregation == "mean"), 1, mv, mp, fuse_dw=False)
+        call("harl_reduce_scalars_set", ptr(net.part_scalars), nblk, ptr(net.scalars), s)
         grad = None
         if want_grad:
             net.backward_trunk(obs, idx, m, seq=seq)
@@ -102,6 +93,9 @@ class HATRPO(OnPolicyBase):
             self._tangent_ws = dict(rows=m, xd=[torch.empty(mp * h, **self.tpdv) for h in hs],
                                     # (zeros: a group's tangent pack keeps the zero rows past its last action, like the pack)
                                     pack_d=torch.zeros_like(net.pack_arena) if net.grouped else torch.empty_like(net.pack_arena))
+            if net.grouped:  # nets._cat_head_fvp: the two halves of every group's logits tangent
+                self._tangent_ws["cat_zd"] = [[torch.empty(mp * sp, **self.tpdv) for sp in net._md_sp] for _ in range(2)]
+                self._tangent_ws["cat_zero_bias"] = torch.zeros(128, **self.tpdv)
             if net.recurrent:
                 H = hs[-1]
                 self._tangent_ws["gates"] = [torch.empty(mp * H, **self.tpdv) for _ in range(4)]  # g_r, g_z, g_nx, g_nh
@@ -170,7 +164,6 @@ class HATRPO(OnPolicyBase):
             else:
                 call("harl_mlp_tangent_hidden", ptr(ws["xd"][l - 1]), ptr(net.xh[l - 1]), m, hs[l - 1], hs[l], ptr(Wp), ptr(Wpd),
                      ptr(bpd), ptr(net.xh[l]), ptr(net.rmask[l]), ptr(net.rstd[l]), ptr(ws["xd"][l]), s, tag="tangent_hidden")
-        fx, fmask, frstd, fh = net.feat()
         xLdot = ws["xd"][-1]
         mv, mp_ = 0, 0
         if net.recurrent and net.gru_wide:  # 128-wide / stacked GRUs: the composed tangent (gru_wide.tangent, round 4)
@@ -192,14 +185,7 @@ class HATRPO(OnPolicyBase):
                  ptr(net.rnn_rstd), H, seq["L"], seq["m_pad"], ptr(ws["ydot"]), s, tag="gru_tangent")
             xLdot = ws["ydot"]
             mv, mp_ = seq["m"], seq["m_pad"]
-        if net.cat_wide:
-            self._cat_head_fvp(m, fx, fh, xLdot, pd, avail, mv, mp_)
-        else:
-            Whp, bhp = net._packs[-1]
-            Whpd, bhpd = packs_d[-1]
-            call("harl_actor_head_fvp", ptr(fx), ptr(xLdot), ptr(fmask), ptr(frstd), m, fh,
-                 ptr(Whp), ptr(bhp), ptr(Whpd), ptr(bhpd), ptr(net.log_std()), net.std_x_coef, net.std_y_coef,
-                 int(net.discrete), net.act_dim, ptr(avail), mv, mp_, ptr(net.dz[0]), ptr(net.dhead), s)
+        net.head_fvp(m, xLdot, pd, avail, mv, mp_, ws.get("cat_zd"), ws.get("cat_zero_bias"))
         net.backward_trunk(obs, idx, m, seq=seq)
         net.unfold_grads()
         g = net.flat_grad
@@ -218,28 +204,6 @@ class HATRPO(OnPolicyBase):
              int(ls_off), net.act_dim, net.std_x_coef, net.std_y_coef, s)
         return out
 
-    def _cat_head_fvp(self, m, fx, fh, xLdot, pack_d, avail, m_valid, m_pad) -> None:
-        """Head part of F v for a Categorical head of 65..512 actions (csrc/cathead.hip): the logits again (the loss or the
-        previous product overwrote the images), per group the two halves of their tangent W'_g x_dot_L and W'_g_dot x_hat_L +
-        b'_g_dot as raw GEMMs, then harl_cat_head_fvp, which leaves the log-softmax backward of q_dot in the logits images --
-        where backward_trunk (md_backward) reads d(loss)/d(logits) after a loss launch.  The groups are layer-table entries:
-        ``pack_d`` holds their W'_g_dot / b'_g_dot at the offsets of the folded packs (harl_fold_tangent_table)."""
-        import ctypes as C
-        net, ws, s = self.actor, self._tangent_ws, stream()
-        rows = ws["xd"][0].numel() // net.hidden_sizes[0]
-        if ws.get("cat_zd") is None:
-            ws["cat_zd"] = [[torch.empty(rows * sp, **self.tpdv) for sp in net._md_sp] for _ in range(2)]
-            ws["cat_zero_bias"] = torch.zeros(128, **self.tpdv)
-        net.md_logits(m)
-        G = len(net._md_sp)
-        for (Wp, _), (pw, pb, _, k), za, zb, sp in zip(net._head_packs, net._pack_slots[-G:], *ws["cat_zd"], net._md_sp):
-            call("harl_mlp_linear", ptr(xLdot), m, fh, sp, ptr(Wp), ptr(ws["cat_zero_bias"]), ptr(za), s, tag="md_linear")
-            call("harl_mlp_linear", ptr(fx), m, fh, sp, ptr(pack_d[pw:pw + sp * k]), ptr(pack_d[pb:pb + sp]), ptr(zb), s,
-                 tag="md_linear")
-        zs, _, sps, n = net.cat_layout()
-        za, zb = [(C.c_void_p * G)(*[t.data_ptr() for t in imgs]) for imgs in ws["cat_zd"]]
-        call("harl_cat_head_fvp", zs, za, zb, G, sps, n, m, ptr(avail), m_valid, m_pad, s, tag="cat_head_fvp")
-
     def _head_outputs(self, obs, m, actions, avail, reuse_trunk=False, seq=None, avail_rows=None) -> torch.Tensor:
         """Distribution parameters at the current weights: Gaussian mean / normalised logits, [rows, act_dim].
         ``reuse_trunk``: a _surrogate() call under the same weights has just left x_hat_L in the workspace.
@@ -250,17 +214,8 @@ class HATRPO(OnPolicyBase):
             out = torch.empty(m, net.act_dim, **self.tpdv)
             self._logp_pass(obs, actions, avail, m, None, head_out=out, reuse_trunk=reuse_trunk)
             return out
-        fx, _, _, fh = net.feat()
-        Wp, bp = net._packs[-1]
         ho = torch.empty(m, net.act_dim, **self.tpdv)
-        if net.cat_wide:
-            net.md_logits(m)
-            call("harl_cat_head_logp", *net.cat_layout(), m, None, None, ptr(avail_rows), None, None, None, None, ptr(ho),
-                 seq["m"], seq["m_pad"], stream(), tag="cat_head_logp")
-        else:
-            call("harl_actor_head_logp", ptr(fx), m, fh, ptr(Wp), ptr(bp), ptr(net.log_std()), net.std_x_coef, net.std_y_coef,
-                 int(net.discrete), net.act_dim, None, ptr(avail_rows), None, None, None, 0, ptr(ho), seq["m"], seq["m_pad"],
-                 stream(), tag="actor_head_logp")
+        net.head_logp(m, avail=avail_rows, head_out=ho, m_valid=seq["m"], m_pad=seq["m_pad"])
         return seq_compact(ho, seq) if seq["m_pad"] != seq["m"] else ho
 
     def _kl_sum(self, head_old, ls_old, head_new, m, acc: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -269,11 +224,7 @@ class HATRPO(OnPolicyBase):
         net = self.actor
         if acc is None:
             acc = torch.zeros(1, dtype=torch.float64, device=self.device)
-        if net.cat_wide:  # rows of 65..512 entries: one wave per row (csrc/cathead.hip)
-            call("harl_cat_kl_sum", ptr(head_old), ptr(head_new), m, net.act_dim, ptr(acc), stream(), tag="cat_kl_sum")
-        else:
-            call("harl_trpo_kl_sum", ptr(head_old), ptr(head_new), ptr(ls_old), ptr(net.log_std()), net.std_x_coef,
-                 net.std_y_coef, m, net.act_dim, int(net.discrete), ptr(acc), stream())
+        net.kl_sum(head_old, ls_old, head_new, m, acc)
         if self.comm.enabled:
             self.comm.all_reduce_sum(acc)
         return acc
@@ -366,20 +317,17 @@ class HATRPO(OnPolicyBase):
         dev = self.device
         obs = _as_dev(obs, dev)
         m = obs.shape[0]
+        seq, rows = None, m
         if self.actor.recurrent:  # gathered [L*m, .] l-major sample + rnn_states [m, 1, H] (recurrent generators)
             HS = self.actor.hidden_sizes[-1] * self.actor.recurrent_n
             nseq = _as_dev(_rnn, dev).shape[0]
             seq = build_seq(dev, m // nseq, nseq, HS, h0=_as_dev(_rnn, dev).reshape(nseq, HS), masks_src=_as_dev(_masks, dev))
-            return self._update_core(obs.reshape(m, -1), seq["L"] * seq["m_pad"], m, _as_dev(actions, dev).reshape(m, -1),
-                                     None if avail is None else _as_dev(avail, dev).reshape(m, -1),
-                                     _as_dev(old_logp, dev).reshape(m, -1), _as_dev(adv, dev).reshape(m), None,
-                                     _as_dev(factor, dev).reshape(m),
-                                     _as_dev(active, dev).reshape(m) if self.use_policy_active_masks else None, seq=seq)
-        return self._update_core(obs.reshape(m, -1), m, m, _as_dev(actions, dev).reshape(m, -1),
+            rows = seq["L"] * seq["m_pad"]
+        return self._update_core(obs.reshape(m, -1), rows, m, _as_dev(actions, dev).reshape(m, -1),
                                  None if avail is None else _as_dev(avail, dev).reshape(m, -1),
                                  _as_dev(old_logp, dev).reshape(m, -1), _as_dev(adv, dev).reshape(m), None,
                                  _as_dev(factor, dev).reshape(m),
-                                 _as_dev(active, dev).reshape(m) if self.use_policy_active_masks else None)
+                                 _as_dev(active, dev).reshape(m) if self.use_policy_active_masks else None, seq=seq)
 
     def train(self, actor_buffer: OnPolicyActorBuffer, advantages, state_type):
         """One full-batch update (hatrpo.py:196-247)."""

@@ -12,6 +12,7 @@ memory and the stream.
 """
 from __future__ import annotations
 
+import ctypes as C
 import math
 import os
 from typing import Dict, List, NamedTuple, Optional, Sequence, Tuple
@@ -521,7 +522,6 @@ class _FlatNet(nn.Module):
         key = (save, gates, self._max_rows)
         hit = self._trunk_cache.get(key)
         if hit is None:
-            import ctypes as C
             L = len(self.hidden_sizes)
             keep = [save or (l == L - 1 and not gates) for l in range(L)]  # activation records a later kernel reads
             vp = lambda ts: (C.c_void_p * len(ts))(*[ptr(t) for t in ts])  # noqa: E731
@@ -859,7 +859,6 @@ class _FlatNet(nn.Module):
     def _backward_gru(self, M: int, seq: dict, s, route: _BwdRoute) -> int:
         """The GRU in front of the layer loop: its recurrence (fused or composed) leaves dz of the last MLP layer in self.dz[1]
         -- the index is returned -- then the six gate blocks of every GRU layer in ONE launch each."""
-        import ctypes as C
         if route.gru == "composed":
             from . import gru_wide
             gru_wide.backward(self, seq)
@@ -970,7 +969,6 @@ class _FlatNet(nn.Module):
         harl_mlp_dw_partials_multi_v (the weight gradients of all MLP layers and of the six gate blocks) -> backward_trunk's combine.
         Each stage is the layer kernel's arithmetic; only the first-layer gradient of 33..63-wide inputs differs from the
         layer path in summation order (that path folds it into harl_mlp_bwd_dx on the matrix-pipe transposes)."""
-        import ctypes as C
         L, po, nwg = len(self.hidden_sizes), self._part_offs, self.n_wg
         spare = [self.dz[2]] if L == 3 else []
         if self.recurrent:
@@ -1048,17 +1046,34 @@ class _FlatNet(nn.Module):
 
     def md_layout(self):
         """(z pointer array, n_groups, sp[], n_heads, nvec[], head_group[]) -- the leading arguments of harl_md_head_*."""
-        import ctypes as C
         G, K = len(self._md_sp), len(self.nvec)
         zs = (C.c_void_p * G)(*[z.data_ptr() for z in self.md_z])
         return (zs, G, (C.c_int * G)(*self._md_sp), K, (C.c_int * K)(*self.nvec), (C.c_int * K)(*self._md_head_group))
 
     def cat_layout(self):
         """(z pointer array, n_groups, sp[], n) -- the leading arguments of harl_cat_head_*."""
-        import ctypes as C
         G = len(self._md_sp)
         zs = (C.c_void_p * G)(*[z.data_ptr() for z in self.md_z])
         return (zs, G, (C.c_int * G)(*self._md_sp), self.act_dim)
+
+    def _cat_head_fvp(self, M: int, xLdot, pack_d, avail, m_valid: int, m_pad: int, zd, zero_bias) -> None:
+        """Head part of F v for a Categorical head of 65..512 actions (csrc/cathead.hip): the logits again (the loss or the
+        previous product overwrote the images), per group the two halves of their tangent W'_g x_dot_L and W'_g_dot x_hat_L +
+        b'_g_dot as raw GEMMs into the caller's scratch images ``zd`` (two lists, one image per group; ``zero_bias``: 128
+        zeros), then harl_cat_head_fvp, which leaves the log-softmax backward of q_dot in the logits images -- where
+        backward_trunk (md_backward) reads d(loss)/d(logits) after a loss launch.  The groups are layer-table entries:
+        ``pack_d`` holds their W'_g_dot / b'_g_dot at the offsets of the folded packs (harl_fold_tangent_table)."""
+        fx, _, _, fh = self.feat()
+        s = stream()
+        self.md_logits(M)
+        G = len(self._md_sp)
+        for (Wp, _), (pw, pb, _, k), za, zb, sp in zip(self._head_packs, self._pack_slots[-G:], *zd, self._md_sp):
+            call("harl_mlp_linear", ptr(xLdot), M, fh, sp, ptr(Wp), ptr(zero_bias), ptr(za), s, tag="md_linear")
+            call("harl_mlp_linear", ptr(fx), M, fh, sp, ptr(pack_d[pw:pw + sp * k]), ptr(pack_d[pb:pb + sp]), ptr(zb), s,
+                 tag="md_linear")
+        zs, _, sps, n = self.cat_layout()
+        za, zb = [(C.c_void_p * G)(*[t.data_ptr() for t in imgs]) for imgs in zd]
+        call("harl_cat_head_fvp", zs, za, zb, G, sps, n, M, ptr(avail), m_valid, m_pad, s, tag="cat_head_fvp")
 
     def md_backward(self, M: int) -> None:
         """d(loss)/d(logits) images (self.md_z, written by harl_md_head_loss / harl_cat_head_loss) -> the groups' weight-gradient partials and
@@ -1214,6 +1229,88 @@ class StochasticPolicy(_FlatNet):
 
     def log_std(self) -> Optional[torch.Tensor]:
         return None if self.discrete else self.pview("act.action_out.log_std")
+
+    # ---- the head's launches on feat(), the head input the trunk forward left: one method per pass, and in each the one place
+    # that tells the three kinds of head apart -- plain (Gaussian, Categorical of up to 64 actions: csrc/heads.hip), MultiDiscrete
+    # groups (self.md) and a Categorical of 65..512 actions (self.cat_wide), the two whose logits md_logits launches first.
+    # Row arrays are tensors or None; m_valid / m_pad: the padded sequences of a recurrent batch (0, 0 otherwise).
+    def dist_args(self):
+        """(log_std, std_x_coef, std_y_coef, discrete, act_dim): the distribution arguments of the plain head's kernels."""
+        return ptr(self.log_std()), self.std_x_coef, self.std_y_coef, int(self.discrete), self.act_dim
+
+    def head_logp(self, M: int, actions=None, avail=None, logp_out=None, old_logp=None, factor=None, head_out=None,
+                  agg: int = 0, m_valid: int = 0, m_pad: int = 0) -> None:
+        """Log-probs of ``actions`` (-> logp_out; with old_logp: their ratio multiplied into ``factor``) and / or the
+        distribution parameters (-> head_out) of rows 0..M-1."""
+        if self.grouped:
+            self.md_logits(M)
+        if self.cat_wide:
+            call("harl_cat_head_logp", *self.cat_layout(), M, None, ptr(actions), ptr(avail), ptr(logp_out), None, ptr(old_logp),
+                 ptr(factor), ptr(head_out), m_valid, m_pad, stream(), tag="cat_head_logp")
+        elif self.md:
+            call("harl_md_head_logp", *self.md_layout(), M, ptr(actions), ptr(logp_out), ptr(old_logp),
+                 0 if old_logp is None else old_logp.shape[1], ptr(factor), agg, ptr(head_out), m_valid, m_pad, stream(),
+                 tag="md_head_logp")
+        else:
+            fx, _, _, fh = self.feat()
+            Wp, bp = self._packs[-1]
+            call("harl_actor_head_logp", ptr(fx), M, fh, ptr(Wp), ptr(bp), *self.dist_args(), ptr(actions), ptr(avail),
+                 ptr(logp_out), ptr(old_logp), ptr(factor), agg, ptr(head_out), m_valid, m_pad, stream(), tag="actor_head_logp")
+
+    def head_loss(self, M: int, idx, actions, avail, old_logp, adv, adv_moments, factor, active, clip: float, ent_coef: float,
+                  agg: int, mode: int, m_valid: int = 0, m_pad: int = 0, logp_out=None, md_ent_scale=None,
+                  fuse_dw: bool = True) -> Tuple[int, bool]:
+        """Loss of rows idx[0..M) and its backward up to the head input (self.dz[0]; grouped heads: d(loss)/d(logits) in the
+        logits images, for md_backward).  ``mode``: 0 clipped (HAPPO), 1 HATRPO's surrogate, 2 unclipped (HAA2C);
+        ``md_ent_scale``: called for the device scalar of HAPPO._md_ent_scale by a MultiDiscrete head, by no other;
+        ``fuse_dw``: let the launch also leave the head's weight-gradient partials, where its kind can (a plain head of up to 32
+        outputs).  Returns (rows of self.part_scalars the launch wrote, head weight gradient done) -- the latter is
+        backward_trunk's ``head_dw_done``."""
+        s = stream()
+        nblk = _lib.load().harl_head_blocks(M)
+        if self.grouped:
+            self.md_logits(M)
+        if self.cat_wide:  # as MultiDiscrete below, ONE softmax over the groups
+            call("harl_cat_head_loss", *self.cat_layout(), M, ptr(idx), ptr(actions), ptr(avail), ptr(old_logp), ptr(adv),
+                 ptr(adv_moments), ptr(factor), ptr(active), clip, ent_coef, mode, m_valid, m_pad, ptr(logp_out),
+                 ptr(self.part_scalars), nblk, s, tag="cat_head_loss")
+            return nblk, False
+        if self.md:  # per-sample loss -> d(logits) in place
+            lay = self.md_layout()
+            call("harl_md_head_loss", lay[0], *lay, M, ptr(idx), ptr(actions), ptr(old_logp), old_logp.shape[1], ptr(adv),
+                 ptr(adv_moments), ptr(factor), ptr(active), ptr(md_ent_scale()), clip, ent_coef, agg, mode, m_valid, m_pad,
+                 ptr(logp_out), ptr(self.part_scalars), nblk, s, tag="md_head_loss")
+            return nblk, False
+        fx, fmask, frstd, fh = self.feat()
+        Wp, bp = self._packs[-1]
+        dw = fuse_dw and not self.wide_head  # (heads of 33..64 actions: separate dW pass)
+        call("harl_actor_head_loss", ptr(fx), ptr(fmask), ptr(frstd), M, fh, ptr(Wp), ptr(bp), *self.dist_args(), ptr(idx),
+             ptr(actions), ptr(avail), ptr(old_logp), ptr(adv), ptr(adv_moments), ptr(factor), ptr(active), clip, ent_coef, agg,
+             mode, m_valid, m_pad, ptr(logp_out), ptr(self.dz[0]), ptr(self.dhead), ptr(self.part_scalars),
+             ptr(self.part[self._part_offs[-1]:]) if dw else None, self.n_wg if fuse_dw else 0, s, tag="actor_head_loss")
+        return (self.n_wg if dw else nblk), dw
+
+    def head_fvp(self, M: int, xLdot, pack_d, avail, m_valid: int, m_pad: int, zd=None, zero_bias=None) -> None:
+        """Head part of a Fisher-vector product: the KL Hessian at the head outputs applied to their tangent -- ``xLdot`` the
+        tangent of the head input, ``pack_d`` the tangent arena laid out like self.pack_arena -- and its backward to the head
+        input, where backward_trunk takes over as after a loss launch.  ``zd`` / ``zero_bias``: _cat_head_fvp's scratch."""
+        if self.cat_wide:
+            return self._cat_head_fvp(M, xLdot, pack_d, avail, m_valid, m_pad, zd, zero_bias)
+        assert not self.md, "no Fisher-vector product of MultiDiscrete heads (HATRPO refuses them)"
+        fx, fmask, frstd, fh = self.feat()
+        (Wp, bp), (pw, pb, o, k) = self._packs[-1], self._pack_slots[-1]
+        call("harl_actor_head_fvp", ptr(fx), ptr(xLdot), ptr(fmask), ptr(frstd), M, fh, ptr(Wp), ptr(bp),
+             ptr(pack_d[pw:pw + o * k]), ptr(pack_d[pb:pb + o]), *self.dist_args(), ptr(avail), m_valid, m_pad, ptr(self.dz[0]),
+             ptr(self.dhead), stream(), tag="actor_head_fvp")
+
+    def kl_sum(self, head_old, ls_old, head_new, M: int, acc) -> None:
+        """acc[0] (fp64) += sum over rows of KL(old || new) of the distributions with the given head outputs (Gaussian: old
+        log_std ``ls_old``, new = the current one)."""
+        if self.cat_wide:  # rows of 65..512 entries: one wave per row (csrc/cathead.hip)
+            call("harl_cat_kl_sum", ptr(head_old), ptr(head_new), M, self.act_dim, ptr(acc), stream(), tag="cat_kl_sum")
+        else:
+            call("harl_trpo_kl_sum", ptr(head_old), ptr(head_new), ptr(ls_old), ptr(self.log_std()), self.std_x_coef,
+                 self.std_y_coef, M, self.act_dim, int(self.discrete), ptr(acc), stream(), tag="trpo_kl_sum")
 
 
 class VNet(_FlatNet):

@@ -187,16 +187,14 @@ class VCritic:
         m = x.shape[0]
         before = self._info.clone()
         self.critic.fold()
+        seq, idx, rows = None, None, m
         if self.critic.recurrent:
             HS = self.critic.hidden_sizes[-1] * self.critic.recurrent_n
             h0 = _as_dev(_rnn, dev)
             seq = build_seq(dev, m // h0.shape[0], h0.shape[0], HS, h0=h0.reshape(-1, HS), masks_src=_as_dev(_masks, dev))
-            self._update_core(x.reshape(m, -1), seq["idx"], seq["L"] * seq["m_pad"], m, _as_dev(value_preds, dev).reshape(m),
-                              _as_dev(returns, dev).reshape(m), value_normalizer, seq=seq)
-            d = self._info - before
-            return d[0], d[1]
-        self._update_core(x.reshape(m, -1), None, m, m, _as_dev(value_preds, dev).reshape(m),
-                          _as_dev(returns, dev).reshape(m), value_normalizer)
+            idx, rows = seq["idx"], seq["L"] * seq["m_pad"]
+        self._update_core(x.reshape(m, -1), idx, rows, m, _as_dev(value_preds, dev).reshape(m),
+                          _as_dev(returns, dev).reshape(m), value_normalizer, seq=seq)
         d = self._info - before
         return d[0], d[1]
 

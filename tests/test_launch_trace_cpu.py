@@ -3,7 +3,10 @@ host side without a GPU (C-ABI calls recorded instead of executed): the launch t
 recorded before the route was decided in one place (tests/golden/launch_traces.json, tools/launch_trace.py), and the image
 contract between prepare_x0n / x0n_multi_item and the forward that follows them.  The recorded matrix also holds the routes of
 the backward (nets._FlatNet._backward_route; configurations 15 and up were recorded before that one was decided in one place):
-BACKWARD_REACHES names what each configuration must go on launching."""
+BACKWARD_REACHES names what each configuration must go on launching.  Configurations 33 and up were recorded before an action
+head's launches moved into nets.StochasticPolicy -- the heads of a train() no earlier configuration has, and the second kind of
+configuration (LT.ACTOR_CONFIGS: the rollout entry points, update() on a gathered sample, the pieces of HATRPO's update):
+HEAD_REACHES names the head launch each of them must go on reaching."""
 import importlib.util
 import json
 import os
@@ -37,7 +40,7 @@ def test_launch_traces_equal_the_recorded_ones(stub_kernels, monkeypatch):  # no
         asked.add((r.kind, r.image, idx_is_none, partial))
         return r
     monkeypatch.setattr(_FlatNet, "_first_launch", spy)
-    got = LT.normalise({k: LT.run_config(k, monkeypatch) for k in LT.CONFIGS})
+    got = LT.normalise({k: LT.run_config(k, monkeypatch) for k in (*LT.CONFIGS, *LT.ACTOR_CONFIGS)})
     diff = LT.compare(want, got)
     assert not diff, "\n".join(diff)
     # ... and the matrix still reaches every route: by the launches in the traces, and by what the route function answered
@@ -47,8 +50,9 @@ def test_launch_traces_equal_the_recorded_ones(stub_kernels, monkeypatch):  # no
     assert {a[2] for a in asked} == {True, False} and {a[3] for a in asked} == {True, False}
     assert {a[:2] for a in asked} == {("act", "cached"), ("panel", "cached"), ("trunk", "cached"), ("wide", "cached"),
                                       ("fused2x", "cached_identity"), ("fused2", "clobbers"), ("input", "clobbers")}
-    # ... and every route of the backward (nets._backward_route): each configuration recorded for one still launches it
-    for name, reaches in BACKWARD_REACHES.items():
+    # ... and every route of the backward (nets._backward_route) and every head launch (HEAD_REACHES): each configuration
+    # recorded for one still launches it
+    for name, reaches in (*BACKWARD_REACHES.items(), *HEAD_REACHES.items()):
         for r in reaches:
             entry_tag, pred = (r, None) if isinstance(r, str) else r
             hits = _launches(got[name], entry_tag)
@@ -61,6 +65,21 @@ def test_launch_traces_equal_the_recorded_ones(stub_kernels, monkeypatch):  # no
     one_layer = {c[0] for c in got["32_h128_obs40_1layer"]}  # L = 1: no hidden layer to go back through
     assert not one_layer & {"harl_mlp_bwd_dx", "harl_mlp_bwd_dx_dw", "harl_mlp_bwd_trunk"}
     assert not _launches(got["32_h128_obs40_1layer"], "harl_mlp_dw_partials:dw_hidden")
+    # the three kinds of head (plain, MultiDiscrete groups, wide Categorical) under each of log-prob, loss and Fisher-vector
+    # product -- MultiDiscrete has no FVP (HATRPO asserts against it) -- and both KL sums
+    heads = {n: {c[0] for c in got[n]} for n in HEAD_REACHES}
+    for what in ("logp", "loss", "fvp"):
+        kinds = ("actor", "cat") if what == "fvp" else ("actor", "md", "cat")
+        assert all(any(f"harl_{kind}_head_{what}" in h for h in heads.values()) for kind in kinds), what
+    assert not any("harl_md_head_fvp" in h for h in heads.values())
+    assert all(any(kl in h for h in heads.values()) for kl in ("harl_trpo_kl_sum", "harl_cat_kl_sum"))
+    # ... exactly one of them per evaluation: a head of one kind never launches a kernel of another
+    for name, (_, _, (space, n), _, _) in LT.ACTOR_CONFIGS.items():
+        kind = "md" if space == "MultiDiscrete" else "cat" if space == "Discrete" and n > 64 else "actor"
+        other = {f"harl_{k}_head_{w}" for k in ("actor", "md", "cat") for w in ("logp", "loss", "fvp") if k != kind}
+        other |= {"harl_trpo_kl_sum" if kind == "cat" else "harl_cat_kl_sum"}
+        assert not heads[name] & other, (name, heads[name] & other)
+        assert (kind == "actor") == ("harl_mlp_linear:md_linear" not in {f"{c[0]}:{c[1] or ''}" for c in got[name]}), name
 
 
 def _launches(trace, entry_tag):
@@ -95,6 +114,61 @@ BACKWARD_REACHES = {
     "32_h128_obs40_1layer": [("harl_mlp_dw_partials:dw_input", lambda a: a[10] == 32)],
     "10_h256x2": ["harl_mlp_panel_bwd:bwd_panel"],
     "11_h128x2_tanh": ["harl_act_bwd:act_bwd"],
+}
+
+
+def _padded(valid: int, pad: int):
+    """Predicate: the (m_valid, m_pad) pair at argument positions ``valid`` / ``pad`` is that of a padded recurrent batch."""
+    return lambda a: 0 < a[valid] < a[pad]
+
+
+def _trpo(clip: int, ent: int, mode: int, valid: int):
+    """Predicate: HATRPO's form of a loss launch -- mode 1, clip and entropy coefficient zero, no log-prob output (the argument
+    after m_pad); ``valid``: position of m_valid."""
+    return lambda a: a[mode] == 1 and a[clip] == 0.0 and a[ent] == 0.0 and a[valid + 2] is None
+
+
+# configuration -> the head launches it was recorded to reach, as in BACKWARD_REACHES.  Argument positions as in
+# include/harl_hip.h: harl_actor_head_logp(.., actions [10], avail, logp_out [12], old_logp, factor, agg, head_out [16], m_valid
+# [17], m_pad), harl_actor_head_loss(.., clip [20], ent [21], agg, trpo [23], m_valid [24], m_pad, logp_out [26], .., dw_part
+# [30], n_wg), harl_actor_head_fvp(.., avail [15], m_valid [16], m_pad), harl_md_head_logp(.., head_out [13], m_valid [14],
+# m_pad), harl_md_head_loss(.., ent_scale [16], clip, ent, agg, mode [20], m_valid [21], ..), harl_cat_head_logp(.., head_out
+# [12], m_valid [13], m_pad), harl_cat_head_loss(.., clip [13], ent [14], mode [15], m_valid [16], m_pad, logp_out [18], ..),
+# harl_cat_head_fvp(.., avail [7], m_valid [8], m_pad), harl_update_fwd_actor(.., clip [22], ent, agg, trpo [25], ..)
+_HATRPO_PLAIN = [("harl_actor_head_loss:actor_head_loss", lambda a: _trpo(20, 21, 23, 24)(a) and a[30] is None and a[31] == 0),
+                 "harl_actor_head_fvp:actor_head_fvp", ("harl_actor_head_logp:actor_head_logp", lambda a: a[12] is None and a[16] is not None),
+                 "harl_trpo_kl_sum:trpo_kl_sum"]
+_HATRPO_CAT = [("harl_cat_head_loss:cat_head_loss", _trpo(13, 14, 15, 16)), "harl_cat_head_fvp:cat_head_fvp",
+               ("harl_cat_head_logp:cat_head_logp", lambda a: a[8] is None and a[12] is not None), "harl_cat_kl_sum:cat_kl_sum"]
+HEAD_REACHES = {
+    "33_md_train": [("harl_md_head_loss:md_head_loss", lambda a: a[23] is not None and a[20] == 0),  # epoch 0 emits log pi_old
+                    ("harl_md_head_logp:md_head_logp", lambda a: a[11] is not None)],                 # the factor pass
+    "34_gru64_discrete100": [("harl_cat_head_loss:cat_head_loss", lambda a: a[16] > 0 and a[17] >= a[16]),
+                             ("harl_cat_head_logp:cat_head_logp", lambda a: a[14] > 0)],
+    "35_haa2c": [("harl_update_fwd_actor:update_fwd", lambda a: a[25] == 2)],
+    "40_happo_md": [("harl_md_head_logp:md_head_logp", lambda a: a[13] is not None and (a[14], a[15]) == (0, 0)),
+                    ("harl_dist_rows:dist_rows", lambda a: a[10] == 2 and a[9] is not None),
+                    ("harl_md_head_loss:md_head_loss", lambda a: a[20] == 0 and a[16] is not None)],
+    "41_happo_gru64_md": [("harl_md_head_logp:md_head_logp", _padded(14, 15)), ("harl_md_head_loss:md_head_loss", _padded(21, 22)),
+                          "harl_critic_head_values:"],
+    "42_happo_gru64x2_box": [("harl_actor_head_logp:actor_head_logp", _padded(17, 18)),
+                             ("harl_actor_head_loss:actor_head_loss", lambda a: _padded(24, 25)(a) and a[30] is not None),
+                             "harl_critic_head_values:"],
+    "43_happo_gru64_discrete200": [("harl_cat_head_logp:cat_head_logp", _padded(13, 14)), ("harl_cat_head_loss:cat_head_loss", _padded(16, 17))],
+    "44_happo_discrete64": [("harl_actor_head_loss:actor_head_loss", lambda a: a[30] is None and a[31] > 0 and a[23] == 0),  # wide_head:
+                            ("harl_mlp_dw_partials:dw_head", lambda a: a[3] == 64),                   # ... the separate dW pass
+                            ("harl_actor_head_logp:actor_head_logp", lambda a: (a[17], a[18]) == (0, 0)), "harl_update_values:update_values"],
+    "45_haa2c_box": [("harl_update_fwd_actor:update_fwd", lambda a: a[25] == 2), "harl_update_logp:update_logp"],
+    "50_hatrpo_box": _HATRPO_PLAIN + ["harl_update_logp:update_logp"],
+    "51_hatrpo_h64_discrete5": _HATRPO_PLAIN + [("harl_actor_head_fvp:actor_head_fvp", lambda a: a[13] == 1 and a[15] is not None)],
+    "52_hatrpo_gru64_box": _HATRPO_PLAIN + ["harl_gru_tangent:gru_tangent", ("harl_actor_head_fvp:actor_head_fvp", _padded(16, 17)),
+                                            ("harl_actor_head_loss:actor_head_loss", _padded(24, 25))],
+    "53_hatrpo_gru128_discrete5": _HATRPO_PLAIN + [("harl_actor_head_fvp:actor_head_fvp", _padded(16, 17))],
+    "54_hatrpo_discrete200": _HATRPO_CAT + [("harl_cat_head_fvp:cat_head_fvp", lambda a: a[7] is not None and (a[8], a[9]) == (0, 0))],
+    "55_hatrpo_gru64_discrete130": _HATRPO_CAT + ["harl_gru_tangent:gru_tangent", ("harl_cat_head_fvp:cat_head_fvp", _padded(8, 9)),
+                                                  ("harl_cat_head_logp:cat_head_logp", _padded(13, 14))],
+    "56_hatrpo_h256_box": _HATRPO_PLAIN + ["harl_head_dw_rows256:dw_head", "harl_mlp_panel_tangent:tangent_panel"],
+    "57_hatrpo_tanh_box": _HATRPO_PLAIN + ["harl_act_ln_tangent:act_ln_tangent"],
 }
 
 

@@ -11,6 +11,10 @@ trace, while addresses and the allocator's reuse of them do not.
     python tools/launch_trace.py --full a.json                             # the full traces (about 400 KB)
     python tools/launch_trace.py --diff a.json b.json                      # first differing call of two --full dumps
 
+A second kind of configuration (ACTOR_CONFIGS) builds one actor directly and records the entry points that evaluate its action
+head -- get_actions, evaluate_actions, update() on a gathered sample, the critic's get_values, the pieces of HATRPO's update --
+which no train() of the first kind reaches.
+
 tests/test_launch_trace_cpu.py runs the comparison of --check in the suite."""
 import argparse
 import ctypes
@@ -62,28 +66,56 @@ CONFIGS = {
     "27_h64x3_obs128": ([64, 64, 64], dict(_SMAC), {}),
     "31_mappo_gru": ([64, 64], dict(_GRU, algo="mappo"), {}),
     "32_h128_obs40_1layer": ([128], dict(obs=40), {}),
+    # ... and the action heads a train() above does not launch: MultiDiscrete groups, a wide Categorical behind a GRU, HAA2C's mode
+    "33_md_train": ([128, 128], dict(nvec=(41, 41, 41, 30)), {}),
+    "34_gru64_discrete100": ([64, 64], dict(_GRU, discrete=100), {}),
+    "35_haa2c": ([128, 128], dict(algo="haa2c", a2c_epoch=2), {}),
+}
+_TRPO = dict(kl_threshold=0.01, ls_step=10, accept_ratio=0.5, backtrack_coeff=0.8)
+_REC = dict(use_recurrent_policy=True)
+_CAT = dict(HARL_TRPO_CAT_WIDE="1")
+# The second kind, name -> (actor class, hidden sizes, action space (class name, argument), model keywords, environment): ONE actor
+# built directly, and the entry points that evaluate its action head instead of a runner's train() (run_actor_config): what no
+# train() of CONFIGS reaches -- the rollout entry points, update() on a gathered sample, every HATRPO launch.
+ACTOR_CONFIGS = {
+    "40_happo_md": ("HAPPO", [128, 128], ("MultiDiscrete", [3, 4]), {}, {}),
+    "41_happo_gru64_md": ("HAPPO", [64], ("MultiDiscrete", [3, 4]), _REC, {}),
+    "42_happo_gru64x2_box": ("HAPPO", [64, 64], ("Box", 3), _REC, {}),
+    "43_happo_gru64_discrete200": ("HAPPO", [64], ("Discrete", 200), _REC, {}),
+    "44_happo_discrete64": ("HAPPO", [128, 128], ("Discrete", 64), {}, {}),
+    "45_haa2c_box": ("HAA2C", [128, 128], ("Box", 3), dict(a2c_epoch=2), {}),
+    "50_hatrpo_box": ("HATRPO", [128, 128], ("Box", 3), {}, {}),
+    "51_hatrpo_h64_discrete5": ("HATRPO", [64, 64], ("Discrete", 5), {}, {}),
+    "52_hatrpo_gru64_box": ("HATRPO", [64, 64], ("Box", 3), _REC, {}),
+    "53_hatrpo_gru128_discrete5": ("HATRPO", [128, 128], ("Discrete", 5), _REC, {}),
+    "54_hatrpo_discrete200": ("HATRPO", [128, 128], ("Discrete", 200), {}, _CAT),
+    "55_hatrpo_gru64_discrete130": ("HATRPO", [64], ("Discrete", 130), _REC, _CAT),
+    "56_hatrpo_h256_box": ("HATRPO", [256, 256], ("Box", 3), {}, {}),
+    "57_hatrpo_tanh_box": ("HATRPO", [128, 128], ("Box", 3), dict(activation_func="tanh"), {}),
 }
 # the switches a configuration may set: cleared around every run, so that the caller's environment does not leak into a trace
 SWITCHES = ("HARL_FUSED_UPDATE", "HARL_BWD_FUSED", "HARL_BWD_K64", "HARL_TRUNK_FUSED", "HARL_GRAPH", "HARL_BWD_STREAMS",
             "HARL_GRU128", "HARL_GRU_COMPOSED", "HARL_NWG", "HARL_X0N_MULTI", "HARL_FOLD_TABLE", "HARL_ALWAYS_FOLD",
-            "HARL_GRU_DW6", "HARL_TRUNK_DW_STREAM", "HARL_LIB")
+            "HARL_GRU_DW6", "HARL_TRUNK_DW_STREAM", "HARL_LIB", "HARL_TRPO_CAT_WIDE", "HARL_UNFOLD_TABLE",
+            "HARL_TANGENT_ONE_LAUNCH")
 
 
-def make_runner(hidden, obs=19, sobs=11, act=3, discrete=0, T=8, N=8, A=2, algo="happo", **over):
-    """tests/test_hybrid_cpu._runner, plus a Discrete(``discrete``) action space and the runner of ``algo``."""
+def make_runner(hidden, obs=19, sobs=11, act=3, discrete=0, nvec=None, T=8, N=8, A=2, algo="happo", **over):
+    """tests/test_hybrid_cpu._runner, plus a Discrete(``discrete``) or MultiDiscrete(``nvec``) action space and the runner of
+    ``algo`` (``over``: a2c_epoch for "haa2c")."""
     from harl_amd.runner import RUNNER_REGISTRY
     from harl_amd.synthetic import Shapes, make_buffers
-    from tests.gpu_checks import Box, Discrete, default_args
+    from tests.gpu_checks import Box, Discrete, MultiDiscrete, default_args
     a = default_args(hidden, ppo_epoch=2, critic_epoch=2, **over)
     train = dict(n_rollout_threads=N, episode_length=T, use_valuenorm=True, use_linear_lr_decay=False,
                  use_proper_time_limits=True, model_dir=None, eval_interval=25, use_eval=False, log_interval=1,
                  num_env_steps=T * N * 2)
-    space = Discrete(discrete) if discrete else Box((act,))
+    space = MultiDiscrete(nvec) if nvec else Discrete(discrete) if discrete else Box((act,))
     r = RUNNER_REGISTRY[algo](dict(algo=algo), dict(train=train, model=dict(a), algo=dict(a)), dict(state_type="EP"),
                                  obs_spaces=[Box((obs,))] * A, share_obs_space=Box((sobs,)), act_spaces=[space] * A,
                                  device=torch.device("cpu"))
-    sh = Shapes(T=T, N=N, A=A, obs_dim=obs, share_obs_dim=sobs, act_dim=discrete or act, discrete=bool(discrete),
-                hidden_sizes=list(hidden))
+    sh = Shapes(T=T, N=N, A=A, obs_dim=obs, share_obs_dim=sobs, act_dim=sum(nvec or ()) or discrete or act,
+                discrete=bool(discrete), hidden_sizes=list(hidden), nvec=list(nvec) if nvec else None)
     d = make_buffers(sh, 4)
     for ag in range(A):
         b = r.actor_buffer[ag]
@@ -162,10 +194,69 @@ class Recorder:
         return a if isinstance(a, (int, float)) else float(a)
 
 
+def run_actor_config(name, rec):
+    """The head-bearing entry points of ONE actor (ACTOR_CONFIGS[name]) into ``rec.trace``: get_actions on one step's rows
+    (deterministic: the stub leaves ``probs`` unwritten), evaluate_actions on all rows, then update() on the gathered sample
+    (HAPPO, HAA2C) next to the critic's get_values -- or, for HATRPO, the pieces of its update that launch (_update_core itself
+    pins host memory and synchronises a stream).  Recurrent: L = 3 steps of m = 8 sequences, padded to the kernels' layout."""
+    import numpy as np
+
+    import harl_amd.happo
+    import harl_amd.hatrpo
+    from harl_amd.nets import build_seq
+    from harl_amd.v_critic import VCritic
+    from tests import gpu_checks as gc
+    cls, hidden, (kind, n), kw, _ = ACTOR_CONFIGS[name]
+    obs_dim, sobs, cpu = 19, 11, torch.device("cpu")
+    space = gc.Box((n,)) if kind == "Box" else getattr(gc, kind)(n)
+    args = gc.default_args(hidden, **_TRPO, **kw)
+    actor = getattr(harl_amd.hatrpo if cls == "HATRPO" else harl_amd.happo, cls)(args, gc.Box((obs_dim,)), space, device=cpu)
+    net = actor.actor
+    rec.nets = {"actor0": net}
+    L, m = (3, 8) if net.recurrent else (1, 24)
+    M, rng = L * m, np.random.default_rng(0)
+    f = lambda *shape: np.ones(shape, np.float32)  # noqa: E731
+    obs = rng.standard_normal((M, obs_dim)).astype(np.float32)
+    act = f(M, net.act_dim) if kind == "Box" else np.zeros((M, len(n) if kind == "MultiDiscrete" else 1), np.float32)
+    avail = f(M, n) if kind == "Discrete" else None
+    rnn, masks = np.zeros((m, net.recurrent_n, hidden[-1]), np.float32), f(M, 1)
+    old_logp = np.full((M, act.shape[1]), -2.0, np.float32)
+    del rec.trace[:]
+    actor.get_actions(obs[:m], rnn, masks[:m], None if avail is None else avail[:m], deterministic=True)
+    # (the distribution object it returns is built from head outputs that no kernel wrote here: padded rows are compacted out
+    # of an uninitialised scratch tensor, so its parameters are not validated)
+    validate = torch.distributions.Distribution._validate_args
+    torch.distributions.Distribution.set_default_validate_args(False)
+    try:
+        actor.evaluate_actions(obs, rnn, act, masks, avail, f(M, 1))
+    finally:
+        torch.distributions.Distribution.set_default_validate_args(validate)
+    if cls != "HATRPO":
+        actor.update((obs, rnn, act, masks, f(M, 1), old_logp, f(M, 1), avail, f(M, 1)))
+        critic = VCritic(args, gc.Box((sobs,)), device=cpu)
+        rec.nets["critic"] = critic.critic
+        critic.get_values(f(M, sobs), rnn, masks)
+        return
+    t = lambda a: None if a is None else torch.from_numpy(a)  # noqa: E731
+    seq, rows, avail_rows = None, M, t(avail)
+    if net.recurrent:
+        HS = hidden[-1] * net.recurrent_n
+        seq = build_seq(cpu, L, m, HS, h0=torch.zeros(m, HS), masks_src=t(masks))
+        rows = L * seq["m_pad"]
+        avail_rows = None if avail is None else torch.ones(rows, n)
+    net.fold()
+    actor._surrogate(t(obs), rows, t(act), t(avail), t(old_logp), torch.ones(M), None, torch.ones(M), torch.ones(M),
+                     want_grad=True, seq=seq)
+    actor._fvp(t(obs), rows, M, avail_rows, torch.zeros(net.n_params), seq=seq)
+    head = actor._head_outputs(t(obs), rows, t(act), t(avail), reuse_trunk=True, seq=seq, avail_rows=avail_rows)
+    actor._kl_sum(head, None if net.discrete else net.log_std().clone(), head, M)
+
+
 def run_config(name, monkeypatch, rounds=2):
-    """The trace of ``rounds`` x (prep_training(); train()) of configuration ``name``.  The caller has installed the stub
-    (the ``stub_kernels`` fixture) on the same ``monkeypatch``."""
-    hidden, kw, env = CONFIGS[name]
+    """The trace of ``rounds`` x (prep_training(); train()) of configuration ``name`` of CONFIGS, or of the entry points of
+    the one actor ``name`` of ACTOR_CONFIGS (run_actor_config).  The caller has installed the stub (the ``stub_kernels``
+    fixture) on the same ``monkeypatch``."""
+    hidden, kw, env = CONFIGS[name] if name in CONFIGS else (None, None, ACTOR_CONFIGS[name][4])
     with monkeypatch.context() as mp:
         for k in SWITCHES:
             mp.delenv(k, raising=False)
@@ -173,6 +264,9 @@ def run_config(name, monkeypatch, rounds=2):
             mp.setenv(k, v)
         rec = Recorder(mp)
         torch.manual_seed(3)
+        if hidden is None:
+            run_actor_config(name, rec)
+            return rec.trace
         r = make_runner(hidden, **kw)
         rec.nets = networks(r)
         del rec.trace[:]
@@ -242,7 +336,7 @@ def all_traces():
     fixture = getattr(stub_kernels, "__wrapped__", None) or stub_kernels.__pytest_wrapped__.obj
     with pytest.MonkeyPatch.context() as mp:
         fixture(mp)
-        return {k: run_config(k, mp) for k in CONFIGS}
+        return {k: run_config(k, mp) for k in (*CONFIGS, *ACTOR_CONFIGS)}
 
 
 def main():
