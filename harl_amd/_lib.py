@@ -66,6 +66,8 @@ SIGNATURES = {
                        _d, _f, _f, _d, _d, _vp, _vp],
     "harl_adam_fold_dev": [_vp, _vp, _vp, _vp, _l, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _i, _f, _i, _i, _vp, _i, _f, _vp, _i,
                            _vp, _d, _d, _f, _f, _vp, _vp],
+    "harl_adam_fold_ls": [_vp, _vp, _vp, _vp, _l, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _i, _f, _i, _i, _vp, _i, _f, _d, _d,
+                          _d, _f, _f, _d, _d, _vp, _vp, _vp],
     "harl_pack_scalars_hilo": [_vp, _vp, _vp],
     "harl_reduce_pack_scalars": [_vp, _i, _vp, _vp, _vp],
     "harl_randperm_replay": [_vp, _l, _l, _vp, _vp, _vp],
@@ -74,6 +76,9 @@ SIGNATURES = {
     "harl_actor_head_logp": [_vp, _l, _i, _vp, _vp, _vp, _f, _f, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _l, _l, _vp],
     "harl_actor_head_loss": [_vp, _vp, _vp, _l, _i, _vp, _vp, _vp, _f, _f, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp,
                              _vp, _vp, _d, _f, _i, _i, _l, _l, _vp, _vp, _vp, _vp, _vp, _i, _vp],
+    "harl_actor_head_loss_ls": [_vp, _vp, _vp, _l, _i, _vp, _vp, _vp, _f, _f, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp,
+                                _vp, _vp, _d, _f, _i, _i, _l, _l, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp],
+    "harl_ls_reduce": [_vp, _i, _vp, _i, _vp],
     "harl_critic_head_values": [_vp, _l, _i, _vp, _vp, _vp, _vp],
     "harl_critic_head_loss": [_vp, _vp, _vp, _l, _i, _vp, _vp, _vp, _vp, _vp, _vp, _f, _i, _i, _f, _l, _l, _vp, _vp, _vp,
                               _vp, _i, _vp],

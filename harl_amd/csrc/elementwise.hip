@@ -1188,14 +1188,17 @@ __device__ __forceinline__ float adam_elem(float g_raw, float pi, float &mi, flo
 // step_idx[0] of the device table hyper[n_hyper][3] = {lr, bias_correction1, bias_correction2} -- the same two host expressions
 // of harl_adam_fold, (float)(lr / bc1) and (float)sqrt(bc2), in IEEE double arithmetic -- so that ONE captured launch serves
 // every replay of a hipGraph.  Every workgroup reads the counter on entry; one thread advances it behind the grid barrier.
-template <bool DEV>
+template <bool DEV, bool LS = false>
 __global__ __launch_bounds__(ADAM_THREADS) void k_adam_fold(
     float *__restrict__ p, float *__restrict__ g, float *__restrict__ m, float *__restrict__ v, long n,
     const float *__restrict__ dwp, const int *__restrict__ tab, int n_layers,
     float *__restrict__ packs, double *__restrict__ scalars, const float *__restrict__ part_scalars, int n_scalar_blocks,
     const float *__restrict__ scalars_hilo, int mode, float const_scale, int logstd_off, int act_dim, double *__restrict__ info, int use_clip, float max_norm,
     float lr_over_bc1, float beta1, float beta2, float omb1, float omb2, float eps, float wd, float bc2_sqrt,
-    unsigned *__restrict__ ws, const double *__restrict__ hyper, int n_hyper, int *step_idx) {
+    unsigned *__restrict__ ws, const double *__restrict__ hyper, int n_hyper, int *step_idx,
+    const double *__restrict__ ls_sum) {
+  // LS (harl_adam_fold_ls): the log_std gradient sums of a Gaussian head of 33..64 dimensions arrive in ls_sum (harl_ls_reduce)
+  // -- the scalar row has room for 32.  Otherwise they are scalars 8 .. 8 + act_dim, as ever (ls_sum is not read).
   __shared__ double sh[64];
   int step_now = 0;
   if constexpr (DEV) {
@@ -1343,7 +1346,7 @@ __global__ __launch_bounds__(ADAM_THREADS) void k_adam_fold(
     for (int b = 0; b < G; b += 4) t += (ws_part[b] + ws_part[b + 1]) + (ws_part[b + 2] + ws_part[b + 3]);  // same order in every workgroup
     if (has_ls)
       for (int d = 0; d < act_dim; ++d) {
-        const float gl = (float)sh[8 + d];
+        const float gl = (float)(LS ? ls_sum[d] : sh[8 + d]);
         t += (double)gl * (double)gl;
       }
     const float norm = (float)(sqrt(t) * fabs((double)scale));
@@ -1357,7 +1360,7 @@ __global__ __launch_bounds__(ADAM_THREADS) void k_adam_fold(
   }
   if (has_ls && blk == 0 && tid < act_dim) {  // log_std: no fold depends on it
     const int i = logstd_off + tid;
-    const float gl = (float)sh[8 + tid];
+    const float gl = (float)(LS ? ls_sum[tid] : sh[8 + tid]);
     g[i] = gl;
     float mi = m[i], vi = v[i];
     p[i] = adam_elem(gl, p[i], mi, vi, C);
@@ -1462,8 +1465,32 @@ extern "C" int harl_adam_fold(float *param, float *grad, float *exp_avg, float *
                      exp_avg_sq, n, dwp, table, n_layers, packs, scalars, part_scalars, n_scalar_blocks,
                      scalars_hilo, mode, const_scale, logstd_off, act_dim, info, use_clip, max_norm, step_size, (float)beta1,
                      (float)beta2, (float)(1.0 - beta1), (float)(1.0 - beta2), eps, weight_decay, bc2_sqrt, (unsigned *)ws,
-                     (const double *)nullptr, 0, (int *)nullptr);
+                     (const double *)nullptr, 0, (int *)nullptr, (const double *)nullptr);
   return check_launch("harl_adam_fold");
+}
+
+// harl_adam_fold for a network whose log_std gradient sums arrive in ls_sum[64] (fp64, harl_ls_reduce) instead of the scalar
+// row: a DiagGaussian head of 33..64 dimensions (harl_actor_head_loss_ls).  Norm and Adam update of log_std[0..act_dim) read
+// ls_sum; everything else is harl_adam_fold.
+extern "C" int harl_adam_fold_ls(float *param, float *grad, float *exp_avg, float *exp_avg_sq, long n, const float *dwp,
+                                 const int *table, int n_layers, float *packs, double *scalars,
+                                 const float *part_scalars, int n_scalar_blocks, const float *scalars_hilo, int mode,
+                                 float const_scale, int logstd_off, int act_dim, double *info, int use_clip, float max_norm,
+                                 double lr, double beta1, double beta2, float eps, float weight_decay, double bias_correction1,
+                                 double bias_correction2, const double *ls_sum, void *ws, void *stream) {
+  if (!ws) { set_error("harl_adam_fold_ls: workspace (>= 32 KiB, zero-initialised once) is required"); return -2; }
+  if (!ls_sum || logstd_off < 0 || act_dim < 1 || act_dim > 64) {
+    set_error("harl_adam_fold_ls: ls_sum, logstd_off >= 0 and act_dim in [1, 64] are required");
+    return -2;
+  }
+  const float step_size = (float)(lr / bias_correction1);
+  const float bc2_sqrt = (float)sqrt(bias_correction2);
+  hipLaunchKernelGGL((k_adam_fold<false, true>), dim3(ADAM_WGS), dim3(ADAM_THREADS), 0, (hipStream_t)stream, param, grad, exp_avg,
+                     exp_avg_sq, n, dwp, table, n_layers, packs, scalars, part_scalars, n_scalar_blocks,
+                     scalars_hilo, mode, const_scale, logstd_off, act_dim, info, use_clip, max_norm, step_size, (float)beta1,
+                     (float)beta2, (float)(1.0 - beta1), (float)(1.0 - beta2), eps, weight_decay, bc2_sqrt, (unsigned *)ws,
+                     (const double *)nullptr, 0, (int *)nullptr, ls_sum);
+  return check_launch("harl_adam_fold_ls");
 }
 
 // harl_adam_fold with {lr, bias_correction1, bias_correction2} taken from row step_idx[0] of a device table (see k_adam_fold)
@@ -1479,7 +1506,7 @@ extern "C" int harl_adam_fold_dev(float *param, float *grad, float *exp_avg, flo
                      exp_avg_sq, n, dwp, table, n_layers, packs, scalars, part_scalars, n_scalar_blocks,
                      scalars_hilo, mode, const_scale, logstd_off, act_dim, info, use_clip, max_norm, 0.f, (float)beta1,
                      (float)beta2, (float)(1.0 - beta1), (float)(1.0 - beta2), eps, weight_decay, 0.f, (unsigned *)ws, hyper,
-                     n_hyper_rows, step_idx);
+                     n_hyper_rows, step_idx, (const double *)nullptr);
   return check_launch("harl_adam_fold_dev");
 }
 
@@ -1867,6 +1894,32 @@ __global__ __launch_bounds__(1024) void k_reduce_scalars_set(const float *__rest
 extern "C" int harl_reduce_scalars_set(const float *part_scalars, int n_blocks, double *scalars, void *stream) {
   hipLaunchKernelGGL(k_reduce_scalars_set, dim3(1), dim3(1024), 0, (hipStream_t)stream, part_scalars, n_blocks, scalars);
   return check_launch("harl_reduce_scalars_set");
+}
+
+// ls_sum[0..64) = column sums, in fp64 and in a fixed order, of the per-workgroup log_std rows part_ls[n_blocks][64] that
+// harl_actor_head_loss_ls writes (one thread per (row group, column), then the 16 row groups in order: no atomics).
+// ACC: add to ls_sum (several minibatch segments in front of one optimiser step) instead of overwriting it.
+template <bool ACC>
+__global__ __launch_bounds__(1024) void k_ls_reduce(const float *__restrict__ pl, int n_blocks, double *__restrict__ out) {
+  __shared__ double sh[16][64];
+  const int j = threadIdx.x & 63, rg = threadIdx.x >> 6;
+  double s = 0;
+  for (int b = rg; b < n_blocks; b += 16) s += (double)pl[(long)b * 64 + j];
+  sh[rg][j] = s;
+  __syncthreads();
+  if (threadIdx.x < 64) {
+    double t = 0;
+#pragma unroll
+    for (int g = 0; g < 16; ++g) t += sh[g][threadIdx.x];
+    out[threadIdx.x] = ACC ? out[threadIdx.x] + t : t;
+  }
+}
+
+extern "C" int harl_ls_reduce(const float *part_ls, int n_blocks, double *ls_sum, int accumulate, void *stream) {
+  if (!part_ls || !ls_sum || n_blocks < 0) { set_error("harl_ls_reduce: part_ls, ls_sum and n_blocks >= 0 are required"); return -2; }
+  if (accumulate) hipLaunchKernelGGL(k_ls_reduce<true>, dim3(1), dim3(1024), 0, (hipStream_t)stream, part_ls, n_blocks, ls_sum);
+  else hipLaunchKernelGGL(k_ls_reduce<false>, dim3(1), dim3(1024), 0, (hipStream_t)stream, part_ls, n_blocks, ls_sum);
+  return check_launch("harl_ls_reduce");
 }
 
 // hipMemsetAsync behind the C ABI (the Python side's `tensor.zero_()` is an ATen fill kernel)

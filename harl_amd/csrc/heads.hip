@@ -200,6 +200,99 @@ __global__ __launch_bounds__(WG_THREADS, (FUSE && DAP <= 8) ? 2 : 1) void k_acto
 }
 
 // =============================================================================================
+// actor head, DiagGaussian of 33..64 dimensions (Box spaces; distributions.py:74-89, act.py:104-157)
+// =============================================================================================
+// k_actor_head<H, 64, false, true> needs ~260 (H = 64) / ~390 (H = 128) registers more than a lane has: the per-dimension
+// actions and stored log-probs one slab ahead (ActorRow<64>), 64 log_std sums, ratios and log-probs next to z, dzh and
+// x_hat_L.  This kernel is the same pipeline -- x_hat_L in registers, VALU head forward, loss, MFMA head backward, dhead as an
+// ATL(64) image for the separate weight-gradient GEMM -- around gauss_wide_sample (heads_common.h), which keeps none of those:
+// no prefetch of the row inputs, the log_std sums in a wave-private LDS tile.  The scalar row stays at 8 sums (PS_STRIDE is
+// wired into the optimiser kernel, the data-parallel message and HATRPO); the 64 log_std sums of a workgroup go to
+// part_ls[blockIdx.x][LS_W] in fixed order (lanes, then waves), for harl_ls_reduce.
+template <int H, bool TRAIN>
+__global__ __launch_bounds__(WG_THREADS, 1) void k_gauss_head_wide(ActorArgs A) {
+  constexpr int DAP = LS_W;
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  float *whl = lds;                      // [2][H/2][DAP]
+  float *cst = whl + 2 * (H / 2) * DAP;  // bias, sigma, logsigma, dsigma_dlogstd, rowsum, 1/sigma, 1/sigma^2  [DAP each]
+  float *red = cst + 7 * DAP;            // [4][PS_STRIDE]
+  double *cd = reinterpret_cast<double *>(red + 4 * PS_STRIDE);  // fp64: 0.5 / sigma^2, log sigma + log sqrt(2 pi)  [DAP each]
+  float *lst = reinterpret_cast<float *>(cd + 2 * DAP);          // TRAIN: [4 waves][LS_W][LS_TS] log_std tiles
+  float *lsr = lst + WAVES_PER_WG * LS_W * LS_TS;  // TRAIN: [4 waves][LS_W]
+  if (TRAIN)
+    for (int e = threadIdx.x; e < WAVES_PER_WG * LS_W * LS_TS; e += WG_THREADS) lst[e] = 0.f;
+  stage_head<H, DAP>(whl, cst, A.Whp, A.bhp, A.act_dim);
+  for (int e = threadIdx.x; e < DAP; e += WG_THREADS) {
+    float sg = 0.5f, sig = 1.f, lsig = 0.f, dsd = 0.f;
+    double sigd = 1.0;
+    if (e < A.act_dim) {  // distributions.py:86-89: std = sigmoid(log_std / x_coef) * y_coef
+      sg = 1.0f / (1.0f + expf(-A.log_std[e] / A.std_x_coef));
+      sig = sg * A.std_y_coef;
+      lsig = logf(sig);
+      dsd = A.std_y_coef * sg * (1.f - sg) / A.std_x_coef;
+      sigd = (double)A.std_y_coef / (1.0 + exp(-(double)A.log_std[e] / (double)A.std_x_coef));
+    }
+    cst[DAP + e] = sig;
+    cst[2 * DAP + e] = lsig;
+    cst[3 * DAP + e] = dsd;
+    cst[5 * DAP + e] = 1.0f / sig;
+    cst[6 * DAP + e] = 1.0f / (sig * sig);
+    cd[e] = 0.5 / (sigd * sigd);  // the importance weight's own log-probs (gauss_wide_sample)
+    cd[DAP + e] = log(sigd) + 0.91893853320467274178;
+  }
+  __syncthreads();
+
+  const int lane = threadIdx.x & 63, wave = wave_id();
+  const int i = lane & 31, h = lane >> 5;
+  const float *whl_h = whl + h * (H / 2) * DAP;
+  float *lsw = lst + wave * (LS_W * LS_TS);
+
+  float adv_mean = 0.f, adv_den = 1.f;
+  if (TRAIN && A.adv_moments) {  // happo.py:122-127
+    const double cnt = A.adv_moments[2];
+    const double m = A.adv_moments[0] / cnt;
+    const double var = A.adv_moments[1] / cnt - m * m;
+    adv_mean = (float)m;
+    adv_den = 1.0f / ((float)sqrt(var > 0 ? var : 0.0) + 1e-5f);
+  }
+  float sc[8];  // 0 loss*active, 1 active, 2 ent*active, 3 ratio, 4 count
+#pragma unroll
+  for (int k = 0; k < 8; ++k) sc[k] = 0.f;
+
+  constexpr int NWM = (H / 2 + 31) / 32;
+  for (long slab = (long)blockIdx.x * WAVES_PER_WG + wave; slab < A.n_slabs; slab += (long)gridDim.x * WAVES_PER_WG) {
+    float z[DAP], dzh[DAP];
+    float s1, s2;
+    if constexpr (TRAIN) {
+      f32x4 xs[H / 8];
+      const uint32_t mb0 = A.relu_mask[(slab * NWM + 0) * WAVE + lane];
+      const uint32_t mb1 = NWM > 1 ? A.relu_mask[(slab * NWM + (NWM - 1)) * WAVE + lane] : 0u;
+      const float rstd = A.rstd[slab * SLAB + i];
+      head_load_regs<H>(A.xL, slab, lane, xs);
+      head_fwd_regs<H, DAP>(xs, whl_h, cst, z);
+      gauss_wide_sample<true>(A, cst, cd, z, slab, lane, adv_mean, adv_den, sc, dzh, s1, s2, lsw);
+      store_dhead<DAP>(A.dhead, slab, lane, dzh);
+      head_bwd_regs_bits<H, DAP>(xs, mb0, mb1, rstd, slab, lane, whl, dzh, s1, s2, A.dzL);
+    } else {
+      head_fwd_stream<H, DAP>(A.xL, slab, lane, whl_h, cst, z);
+      gauss_wide_sample<false>(A, cst, cd, z, slab, lane, adv_mean, adv_den, sc, dzh, s1, s2, lsw);
+    }
+  }
+
+  if constexpr (TRAIN) {
+    block_reduce_store<8>(sc, red, A.part_scalars + (long)blockIdx.x * PS_STRIDE);  // (its barrier: every wave's tile is complete)
+    float t = 0.f;  // lane = dimension: the wave's 32 sample lanes in order
+#pragma unroll 8
+    for (int s = 0; s < SLAB; ++s) t += lsw[lane * LS_TS + s];
+    lsr[wave * LS_W + lane] = t;
+    __syncthreads();
+    if (threadIdx.x < LS_W)
+      A.part_ls[(long)blockIdx.x * LS_W + threadIdx.x] = (lsr[threadIdx.x] + lsr[LS_W + threadIdx.x]) +
+                                                         (lsr[2 * LS_W + threadIdx.x] + lsr[3 * LS_W + threadIdx.x]);
+  }
+}
+
+// =============================================================================================
 // critic head
 // =============================================================================================
 
@@ -515,11 +608,37 @@ void launch_actor(const ActorArgs &A, int grid, hipStream_t s) {
   hipLaunchKernelGGL((k_actor_head<H, DAP, DISC, TRAIN>), dim3(grid), dim3(WG_THREADS), base, s, A);
 }
 
+template <int H, bool TRAIN>
+void launch_gauss_wide(const ActorArgs &A, int grid, hipStream_t s) {
+  size_t fl = (size_t)2 * (H / 2) * LS_W + 7 * LS_W + 4 * PS_STRIDE + 2 * 2 * LS_W;  // (the last: 2 x LS_W doubles)
+  if (TRAIN) fl += (size_t)WAVES_PER_WG * LS_W * LS_TS + (size_t)WAVES_PER_WG * LS_W;  // log_std tiles + their wave sums
+  const size_t shm = fl * sizeof(float);
+  allow_big_lds(k_gauss_head_wide<H, TRAIN>, shm);  // (training: 53.5 KiB at H = 64, 69.5 KiB at H = 128)
+  hipLaunchKernelGGL((k_gauss_head_wide<H, TRAIN>), dim3(grid), dim3(WG_THREADS), shm, s, A);
+}
+
 template <bool TRAIN>
 int dispatch_actor(const ActorArgs &A, int H, int discrete, int grid, hipStream_t s) {
   const int D = A.act_dim;
+  if (!discrete && D > 32 && D <= LS_W) {  // Gaussian heads of 33..64 dimensions: their own kernel, their own loss entry point
+    if (TRAIN && (!A.part_ls || A.dw_part)) {
+      set_error("actor head: Gaussian heads of 33..64 dimensions train through harl_actor_head_loss_ls (part_ls, dw_part = NULL)");
+      return -2;
+    }
+    if (H != 64 && H != 128) {
+      set_error("actor head: Gaussian heads of 33..64 dimensions need a hidden width of 64 or 128");
+      return -2;
+    }
+    if (H == 64) launch_gauss_wide<64, TRAIN>(A, grid, s);
+    else launch_gauss_wide<128, TRAIN>(A, grid, s);
+    return check_launch("harl_actor_head");
+  }
+  if (A.part_ls) {
+    set_error("harl_actor_head_loss_ls: Gaussian heads of 33..64 dimensions only");
+    return -2;
+  }
   if (D < 1 || D > 64 || (D > 32 && !discrete)) {
-    set_error("actor head: act_dim must be in [1, 32] (Categorical heads: [1, 64])");
+    set_error("actor head: act_dim must be in [1, 64]");
     return -2;
   }
   if (D > 32 && A.dw_part) {
@@ -570,16 +689,17 @@ extern "C" int harl_actor_head_logp(const float *xL, long M, int H, const float 
   return dispatch_actor<false>(A, H, discrete, head_grid(M), (hipStream_t)stream);
 }
 
-extern "C" int harl_actor_head_loss(const float *xL, const uint32_t *relu_mask, const float *rstd, long M, int H,
-                                    const float *Whp, const float *bhp, const float *log_std, float std_x_coef,
-                                    float std_y_coef, int discrete, int act_dim, const int64_t *idx,
-                                    const float *actions, const float *avail, const float *old_logp, const float *adv,
-                                    const double *adv_moments, const float *factor, const float *active,
-                                    double clip_param, float entropy_coef, int agg_mean, int trpo, long m_valid,
-                                    long m_pad, float *logp_out, float *dzL, float *dhead, float *part_scalars,
-                                    float *dw_part, int n_wg, void *stream) {
+static int actor_head_loss(const float *xL, const uint32_t *relu_mask, const float *rstd, long M, int H,
+                           const float *Whp, const float *bhp, const float *log_std, float std_x_coef,
+                           float std_y_coef, int discrete, int act_dim, const int64_t *idx,
+                           const float *actions, const float *avail, const float *old_logp, const float *adv,
+                           const double *adv_moments, const float *factor, const float *active,
+                           double clip_param, float entropy_coef, int agg_mean, int trpo, long m_valid,
+                           long m_pad, float *logp_out, float *dzL, float *dhead, float *part_scalars,
+                           float *dw_part, int n_wg, float *part_ls, void *stream) {
   if (M <= 0) return 0;
   ActorArgs A{};
+  A.part_ls = part_ls;
   A.trpo = trpo;
   A.logp_out = logp_out;
   A.dw_part = dw_part;
@@ -592,6 +712,38 @@ extern "C" int harl_actor_head_loss(const float *xL, const uint32_t *relu_mask, 
   A.clip_lo = (float)(1.0 - clip_param); A.clip_hi = (float)(1.0 + clip_param);  // torch.clamp(imp, 1 - c, 1 + c): Python doubles
   A.agg_mean = agg_mean; A.dzL = dzL; A.dhead = dhead; A.part_scalars = part_scalars; A.n_slabs = n_slabs_of(M);
   return dispatch_actor<true>(A, H, discrete, dw_part ? n_wg : head_grid(M), (hipStream_t)stream);
+}
+
+extern "C" int harl_actor_head_loss(const float *xL, const uint32_t *relu_mask, const float *rstd, long M, int H,
+                                    const float *Whp, const float *bhp, const float *log_std, float std_x_coef,
+                                    float std_y_coef, int discrete, int act_dim, const int64_t *idx,
+                                    const float *actions, const float *avail, const float *old_logp, const float *adv,
+                                    const double *adv_moments, const float *factor, const float *active,
+                                    double clip_param, float entropy_coef, int agg_mean, int trpo, long m_valid,
+                                    long m_pad, float *logp_out, float *dzL, float *dhead, float *part_scalars,
+                                    float *dw_part, int n_wg, void *stream) {
+  return actor_head_loss(xL, relu_mask, rstd, M, H, Whp, bhp, log_std, std_x_coef, std_y_coef, discrete, act_dim, idx, actions,
+                         avail, old_logp, adv, adv_moments, factor, active, clip_param, entropy_coef, agg_mean, trpo, m_valid,
+                         m_pad, logp_out, dzL, dhead, part_scalars, dw_part, n_wg, nullptr, stream);
+}
+
+// harl_actor_head_loss for a DiagGaussian head of 33..64 dimensions (k_gauss_head_wide): the scalar row keeps its 8 sums, the
+// per-dimension log_std sums of every workgroup go to part_ls[harl_head_blocks(M)][64]
+extern "C" int harl_actor_head_loss_ls(const float *xL, const uint32_t *relu_mask, const float *rstd, long M, int H,
+                                       const float *Whp, const float *bhp, const float *log_std, float std_x_coef,
+                                       float std_y_coef, int discrete, int act_dim, const int64_t *idx,
+                                       const float *actions, const float *avail, const float *old_logp, const float *adv,
+                                       const double *adv_moments, const float *factor, const float *active,
+                                       double clip_param, float entropy_coef, int agg_mean, int trpo, long m_valid,
+                                       long m_pad, float *logp_out, float *dzL, float *dhead, float *part_scalars,
+                                       float *dw_part, int n_wg, float *part_ls, void *stream) {
+  if (!part_ls || dw_part || discrete || act_dim <= 32 || act_dim > 64) {
+    set_error("harl_actor_head_loss_ls: a Gaussian head of 33..64 dimensions, part_ls and dw_part = NULL are required");
+    return -2;
+  }
+  return actor_head_loss(xL, relu_mask, rstd, M, H, Whp, bhp, log_std, std_x_coef, std_y_coef, discrete, act_dim, idx, actions,
+                         avail, old_logp, adv, adv_moments, factor, active, clip_param, entropy_coef, agg_mean, trpo, m_valid,
+                         m_pad, logp_out, dzL, dhead, part_scalars, dw_part, n_wg, part_ls, stream);
 }
 
 extern "C" int harl_critic_head_values(const float *xL, long M, int H, const float *Whp, const float *bhp,

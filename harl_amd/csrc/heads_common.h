@@ -34,6 +34,7 @@ struct ActorArgs {
   int trpo;         // surrogate: 0 HAPPO (clipped, happo.py:71-85); 1 HATRPO +ratio*f*adv*active, no entropy term
                     // (hatrpo.py:82-90); 2 HAA2C -ratio*f*adv*active, no clip (haa2c.py:70-80)
   long n_slabs;
+  float *part_ls;   // Gaussian heads of 33..64 dimensions: per-workgroup log_std sums [gridDim.x][LS_W] (k_gauss_head_wide)
 };
 
 template <int H, int DAP>
@@ -775,6 +776,148 @@ __device__ __forceinline__ bool actor_sample(const ActorArgs &A, const float *cs
   for (int d = 0; d < DAP; ++d) {
     s1 += dzh[d] * cst[4 * DAP + d];
     s2 += dzh[d] * zlin[d];
+  }
+  s1_out = s1;
+  s2_out = s2;
+  return true;
+}
+
+// ---------------------------------------------------------------------------------------------
+// DiagGaussian heads of 33..64 dimensions (k_gauss_head_wide, heads.hip; distributions.py:74-89, act.py:104-157):
+// actor_sample's arithmetic for a 64-column head, arranged so that per dimension only the head outputs z and (training) their
+// gradient dzh live in registers.  actor_sample keeps actions, stored log-probs (both one slab ahead), log-probs, ratios and the
+// log_std sums per dimension as well, which at 64 columns is several hundred registers more than a lane has.  Here
+//   - actions and stored log-probs are read where they are used, 16 dimensions at a time (clamped index: no load under a branch);
+//   - the dimensions are swept twice -- log-probs / ratios / entropy -> the importance weight, then the gradient, which
+//     recomputes the per-dimension ratio under `mean` aggregation instead of keeping 64 of them;
+//   - the importance weight is formed in fp64 (cd: fp64 0.5 / sigma^2 and log sigma + log sqrt(2 pi) per dimension): the sum of
+//     logp_d - old_logp_d and one exp per row (`mean`: expf of the fp64 difference, summed in fp64).  A product of up to 64 fp32
+//     exponentials of differences of rounded log-probs is good to ~1e-6 per row, and the first agent's policy loss is a mean of
+//     ratio x normalised advantage that cancels to ~1 % of its terms.  The emitted log-probs and the gradient sweep stay fp32;
+//   - d(loss)/d(log_std_d) accumulates per (dimension, sample lane) in a wave-private LDS tile lsw[LS_W][LS_TS] (row stride 33:
+//     lane i at d * 33 + i is conflict-free, and so is the column sweep of the epilogue); the scalar row keeps its 8 sums.
+//   - the action width is re-read as an opaque scalar per chunk: left loop-invariant, hipcc hoists all 2 x 64 `d < act_dim`
+//     tests out of the slab loop and keeps their results in ~500 SGPRs, which it spills into VGPR lanes (and those, with the
+//     rest, into scratch: 9 / 38 registers at H = 64 / 128); re-read, each test is an s_cmp at its point of use.
+// Padding dimensions (d >= act_dim) and samples that do not count get exactly 0 in dzh and add nothing to the tile.
+// ---------------------------------------------------------------------------------------------
+constexpr int LS_W = 64;   // columns of a part_ls row and of ls_sum
+constexpr int LS_TS = 33;  // row stride of a wave's log_std tile
+
+template <bool TRAIN>
+__device__ __forceinline__ bool gauss_wide_sample(const ActorArgs &A, const float *cst, const double *cd, const float (&z)[LS_W],
+                                                  long slab, int lane, float adv_mean, float adv_den, float (&sc)[8], float (&dzh)[LS_W],
+                                                  float &s1_out, float &s2_out, float *lsw) {
+  constexpr int DAP = LS_W, CH = 16;
+  const int i = lane & 31, h = lane >> 5;
+  const int D = A.act_dim;
+  const float inv_D = uniform_f(1.0f / (float)D);
+  const long j = slab * SLAB + i;
+  const bool valid = j < A.M && (A.m_pad == 0 || (j % A.m_pad) < A.m_valid);
+  const long jc = j < A.M ? j : A.M - 1;
+  const long row = A.idx ? A.idx[jc] : jc;
+  const long orow = TRAIN ? row : jc;
+  const bool has_olp = TRAIN || A.old_logp;
+  const bool emit = valid && h == 0;
+  // absent arrays: a mapped dummy row (the head weights, >= 33 floats); the consumers test the same pointers
+  const float *ap = A.actions ? A.actions + row * D : A.Whp;
+  const float *op = has_olp ? A.old_logp + orow * D : A.Whp;
+
+  float ent = 0.f;
+  double lsum = 0.0, rsum = 0.0;  // prod: sum_d (logp_d - old_logp_d) ; mean: sum_d exp(logp_d - old_logp_d)
+#pragma unroll
+  for (int c = 0; c < DAP / CH; ++c) {
+    float a[CH], o[CH];
+    int Dc = D;
+    asm volatile("" : "+s"(Dc));  // opaque per chunk (see above: the 64 width tests must not be hoisted out of the slab loop)
+#pragma unroll
+    for (int k = 0; k < CH; ++k) {
+      const int d = CH * c + k, dl = d < Dc ? d : 0;
+      a[k] = ap[dl];
+      o[k] = op[dl];
+    }
+#pragma unroll
+    for (int k = 0; k < CH; ++k) {
+      const int d = CH * c + k;
+      if (d < Dc) {
+        const float lsig = cst[2 * DAP + d];
+        const float av = A.actions ? a[k] : z[d];  // actions == NULL: head outputs only
+        const float diff = av - z[d];
+        const float lp = -(diff * diff) * (0.5f * cst[6 * DAP + d]) - lsig - LOG_SQRT_2PI;  // torch Normal.log_prob
+        ent += HALF_LOG_2PI_PLUS_HALF + lsig;
+        if (has_olp) {
+          const double dd = (double)av - (double)z[d];
+          const double dl = -(dd * dd) * cd[d] - cd[DAP + d] - (double)o[k];
+          lsum += dl;
+          if (A.agg_mean) rsum += (double)expf((float)dl);
+        }
+        if (emit) {
+          if (!TRAIN && A.head_out) A.head_out[j * D + d] = z[d];
+          if (A.logp_out) A.logp_out[j * D + d] = lp;
+        }
+      }
+    }
+  }
+  const float imp = A.agg_mean ? (float)(rsum * (double)inv_D) : (float)exp(lsum);
+  if (!TRAIN) {
+    if (emit && A.factor_out) A.factor_out[j] = A.factor_out[j] * imp;  // on_policy_ha_runner.py:116-124
+    return false;
+  }
+
+  // ---------------- loss + backward (happo.py:66-91), as actor_sample ----------------
+  const float act = A.active ? A.active[row] : 1.f;
+  const float advn = (A.adv[row] - adv_mean) * adv_den;
+  const float fct = A.factor_in ? A.factor_in[row] : 1.f;
+  const float lo = A.clip_lo, hi = A.clip_hi;
+  const float surr1 = imp * advn;
+  const float impc = fminf(fmaxf(imp, lo), hi);
+  const float surr2 = impc * advn;
+  const float mn = fminf(surr1, surr2);
+  const float inrange = (imp >= lo && imp <= hi) ? 1.f : 0.f;
+  float gsel = surr1 < surr2 ? 1.f : (surr1 > surr2 ? inrange : 0.5f + 0.5f * inrange);
+  if (A.trpo != 0) gsel = 1.f;
+  const float dimp = valid ? (A.trpo == 1 ? fct * act * advn : -fct * act * advn * gsel) : 0.f;
+  const float ecoef = (valid && A.trpo != 1) ? -A.entropy_coef * act : 0.f;
+  if (emit) {
+    sc[0] += A.trpo == 1 ? surr1 * fct * act : -fct * (A.trpo == 2 ? surr1 : mn) * act;
+    sc[1] += act;
+    sc[2] += ent * act;
+    sc[3] += imp;
+    sc[4] += 1.f;
+  }
+  float s1 = 0.f, s2 = 0.f;
+#pragma unroll
+  for (int c = 0; c < DAP / CH; ++c) {
+    float a[CH], o[CH];
+    int Dc = D;
+    asm volatile("" : "+s"(Dc));  // opaque per chunk (see above: the 64 width tests must not be hoisted out of the slab loop)
+#pragma unroll
+    for (int k = 0; k < CH; ++k) {
+      const int d = CH * c + k, dl = d < Dc ? d : 0;
+      a[k] = ap[dl];
+      o[k] = op[dl];
+    }
+#pragma unroll
+    for (int k = 0; k < CH; ++k) {
+      const int d = CH * c + k;
+      float g = 0.f;
+      if (d < Dc) {
+        const float diff = a[k] - z[d];
+        const float isig = cst[5 * DAP + d], ivar = cst[6 * DAP + d];  // 1/sigma, 1/sigma^2 (prologue)
+        float w = imp;  // d imp / d logp_d : prod -> imp ; mean -> r_d / D
+        if (A.agg_mean) {
+          const float lp = -(diff * diff) * (0.5f * ivar) - cst[2 * DAP + d] - LOG_SQRT_2PI;
+          w = expf(lp - o[k]) * inv_D;
+        }
+        const float dlp = dimp * w;
+        g = valid ? dlp * diff * ivar : 0.f;
+        const float dsig = dlp * (diff * diff * ivar * isig - isig) + ecoef * isig;
+        if (emit) lsw[d * LS_TS + i] += dsig * cst[3 * DAP + d];
+        s1 += g * cst[4 * DAP + d];
+        s2 += g * (z[d] - cst[d]);
+      }
+      dzh[d] = g;
+    }
   }
   s1_out = s1;
   s2_out = s2;

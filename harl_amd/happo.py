@@ -16,6 +16,7 @@ import torch
 from . import _lib, graphs
 from ._lib import PS_STRIDE, call, ptr, stream
 from .buffers import OnPolicyActorBuffer, consume_randperm, minibatch_indices, rng_sync
+from .configs import GAUSS_WIDE_REFUSALS
 from .dist import Comm, local_minibatch_rows
 from .nets import FusedAdam, StochasticPolicy, build_seq, routing_switches, seq_compact
 from .valuenorm import _as_dev
@@ -43,6 +44,7 @@ class OnPolicyBase:
         self.actor_optimizer = FusedAdam(self.actor, self.lr, self.opti_eps, self.weight_decay)
         self.comm = Comm()
         self.shard = None  # (n_global, lo, hi) when n_rollout_threads is sharded across ranks
+        self._refuse_gauss_wide_dp()
         self._old_logp: Optional[torch.Tensor] = None
         self._graph = graphs.GraphedStep("the actor")  # HARL_GRAPH=1: captured optimiser steps (HAPPO / HAA2C / MAPPO)
         self._graph_bufs: dict = {}   # persistent copies of what arrives as a fresh tensor per train()
@@ -52,12 +54,18 @@ class OnPolicyBase:
         """dict(captures, replays, eager_steps) of this actor's optimiser steps under HARL_GRAPH=1 (all zero without it)."""
         return self._graph.stats()
 
+    def _refuse_gauss_wide_dp(self) -> None:
+        """Gaussian heads of 33..64 dimensions: their log_std sums (net.ls_sum) are not part of the data-parallel message."""
+        if self.actor.gauss_wide and (self.comm.enabled or self.shard is not None):
+            raise NotImplementedError(GAUSS_WIDE_REFUSALS["dp"])
+
     def _graph_config_ok(self) -> bool:
         """HARL_GRAPH=1 and a configuration whose optimiser steps may be replayed from a hipGraph: feed-forward, one action
         head (Gaussian / Categorical of up to 64 actions), no data parallelism.  Everything else stays eager, exactly as without
         the variable."""
         return (graphs.enabled() and not (self.use_recurrent_policy or self.use_naive_recurrent_policy)
-                and not self.actor.recurrent and not self.actor.grouped and not self.comm.enabled and self.shard is None)
+                and not self.actor.recurrent and not self.actor.grouped and not self.actor.gauss_wide
+                and not self.comm.enabled and self.shard is None)
 
     def _graph_stage(self, name: str, t: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
         """Copy ``t`` into this actor's persistent buffer ``name`` (a captured step holds ADDRESSES)."""
@@ -319,6 +327,11 @@ class HAPPO(OnPolicyBase):
             sc.zero_()
             nblk = None
         ps_kw = dict(part_scalars=net.part_scalars, n_scalar_blocks=nblk) if nblk is not None else {}
+        if net.gauss_wide:  # (nblk None: the segments' sums were accumulated, as net.scalars)
+            self._refuse_gauss_wide_dp()
+            if nblk is not None:
+                net.ls_reduce(nblk, accumulate=False)
+            ps_kw["ls_sum"] = net.ls_sum
         if self.comm.enabled:  # ONE collective per optimiser step: [folded gradients | loss scalars] (dist.py)
             hilo = net.dwp_msg[net.total_dwp:]
             if nblk is not None:  # partial rows -> fp64 sums -> fixed-grid fp32 pieces behind the gradients, one launch
@@ -343,7 +356,7 @@ class HAPPO(OnPolicyBase):
                                           logp_out=logp_out)
             self._optimizer_step(nblk)
         if not _graph:
-            if self.actor.cat_wide and graphs.enabled():  # HARL_GRAPH=1: wide Categorical heads run eagerly, and say so
+            if (self.actor.cat_wide or self.actor.gauss_wide) and graphs.enabled():  # HARL_GRAPH=1: these heads run eagerly, and say so
                 self._graph.eager_steps += 1
             return step()
         # HARL_GRAPH=1 (graphs.py): replay this step from a hipGraph.  Eager all the same: the epoch-0 step that also emits the

@@ -18,7 +18,7 @@ import torch
 from . import _lib
 from ._lib import call, ptr, stream
 from .buffers import OnPolicyActorBuffer, consume_randperm, rng_sync
-from .configs import CAT_WIDE_REFUSALS, trpo_cat_wide_enabled
+from .configs import CAT_WIDE_REFUSALS, GAUSS_WIDE_REFUSALS, gauss_wide_enabled, trpo_cat_wide_enabled
 from .happo import OnPolicyBase
 from .nets import build_seq, consume_policy_init_rng, seq_compact
 from .valuenorm import _as_dev
@@ -30,6 +30,9 @@ class HATRPO(OnPolicyBase):
             "only continuous and discrete action space is supported by HATRPO."
         if act_space.__class__.__name__ == "Discrete" and int(act_space.n) > 64 and not trpo_cat_wide_enabled():
             raise NotImplementedError(CAT_WIDE_REFUSALS["hatrpo"] if int(act_space.n) <= 512 else CAT_WIDE_REFUSALS["n"])
+        if act_space.__class__.__name__ == "Box" and int(act_space.shape[0]) > 32 and gauss_wide_enabled():
+            # (harl_actor_head_fvp, harl_trpo_begin and the line search read the log_std block from the scalar row)
+            raise NotImplementedError(GAUSS_WIDE_REFUSALS["hatrpo" if int(act_space.shape[0]) <= 64 else "n"])
         super().__init__(args, obs_space, act_space, device)  # (HARL_TRPO_CAT_WIDE=1: n > 512, 256-wide and non-ReLU are refused there)
         if self.actor.cat_wide and self.actor.recurrent and self.actor.gru_wide:
             raise NotImplementedError(CAT_WIDE_REFUSALS["hatrpo_gru_wide"])

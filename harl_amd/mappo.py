@@ -97,7 +97,7 @@ class MAPPO(HAPPO):
                     segs.append(None if ind is None else self._graph_stage(f"idx{a}", ind) if graph else ind.to(dev))
                 if graph and self._share_param_step_graphed(actor_buffer, segs, adv_a, moments, acc, A, B):
                     continue
-                if net.cat_wide and graphs.enabled():  # (HAPPO._update_core: eager under HARL_GRAPH=1, counted)
+                if (net.cat_wide or net.gauss_wide) and graphs.enabled():  # (HAPPO._update_core: eager under HARL_GRAPH=1, counted)
                     self._graph.eager_steps += 1
                 acc.zero_()
                 net._ensure_ws(B)
@@ -122,6 +122,8 @@ class MAPPO(HAPPO):
                         buf.flat("active_masks").reshape(B) if self.use_policy_active_masks else None)
                     acc.add_(net.dwp)
                     call("harl_reduce_scalars", ptr(net.part_scalars), nblk, ptr(net.scalars), s)  # accumulates
+                    if net.gauss_wide:  # ... and so do the log_std sums of a 33..64-dimensional Gaussian head (first segment: set)
+                        net.ls_reduce(nblk, accumulate=a > 0)
                 self._md_ent_override = None
                 net.dwp.copy_(acc)
                 self._optimizer_step(None)

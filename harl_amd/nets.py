@@ -23,7 +23,7 @@ import torch.nn as nn
 from . import _lib
 from . import graphs as _graphs
 from ._lib import DHEAD_LD, PS_STRIDE, SLAB, call, ptr, stream
-from .configs import CAT_WIDE_REFUSALS, bwd_k64, bwd_streams, gru_dw6, trunk_dw_stream
+from .configs import CAT_WIDE_REFUSALS, GAUSS_WIDE_REFUSALS, bwd_k64, bwd_streams, gauss_wide_enabled, gauss_wide_reason, gru_dw6, trunk_dw_stream
 
 SUPPORTED_WIDTHS = (64, 128, 256)
 # models_tools.py:28-50; ids of csrc/elementwise.hip (0 = the fused ReLU kernels)
@@ -185,6 +185,7 @@ class _FlatNet(nn.Module):
         self._x0n_force = False  # build the image whatever the cache says (graphs.py: several buffers inside ONE captured step)
         self.md = False  # MultiDiscrete heads (StochasticPolicy)
         self.cat_wide = False  # Categorical head of 65..512 actions, cut into groups of 128 rows (StochasticPolicy)
+        self.gauss_wide = False  # Gaussian head of 33..64 dimensions, HARL_GAUSS_WIDE=1 (StochasticPolicy)
         self._md_sp: List[int] = []  # image width of every head GROUP (MultiDiscrete / wide Categorical), empty otherwise
         self._cpu_params: List[Tuple[str, torch.Tensor]] = []
         self._build_trunk_params(args)
@@ -483,6 +484,11 @@ class _FlatNet(nn.Module):
                 gru_wide.ensure_ws(self, mp)
         self.n_head_blocks = max(_lib.load().harl_head_blocks(M), self.n_wg)
         self.part_scalars = torch.zeros(self.n_head_blocks * PS_STRIDE, dtype=f32, device=dev)
+        if self.gauss_wide:
+            # the scalar row holds 32 per-dimension log_std sums: the 64 of these heads go through rows of their own
+            # (harl_actor_head_loss_ls -> harl_ls_reduce -> harl_adam_fold_ls)
+            self.part_ls = torch.zeros(self.n_head_blocks * 64, dtype=f32, device=dev)
+            self.ls_sum = torch.zeros(64, dtype=torch.float64, device=dev)
         self.scalars = torch.zeros(PS_STRIDE, dtype=torch.float64, device=dev)
         self._max_rows = M
 
@@ -1149,7 +1155,9 @@ class StochasticPolicy(_FlatNet):
             raise NotImplementedError(f"action space {self.action_type}")
         if self.action_type == "Discrete" and self.act_dim > 64:
             self._init_cat_wide()
-        if not self.grouped and (self.act_dim > 64 or (self.act_dim > 32 and not self.discrete)):
+        if self.action_type == "Box" and self.act_dim > 32 and gauss_wide_enabled():
+            self._init_gauss_wide()
+        if not self.grouped and not self.gauss_wide and (self.act_dim > 64 or (self.act_dim > 32 and not self.discrete)):
             raise NotImplementedError("action heads wider than 32 (Categorical: 64) are not instantiated")
         self.wide_head = (not self.grouped) and self.act_dim > 32
         self._finalize_params()
@@ -1170,6 +1178,22 @@ class StochasticPolicy(_FlatNet):
         self.cat_wide = True
         self._cat_rows = [min(128, n - lo) for lo in range(0, n, 128)]
         self._md_sp = [64 if r <= 64 else 128 for r in self._cat_rows]
+
+    def _init_gauss_wide(self) -> None:
+        """DiagGaussian(hidden, n) with 33 <= n <= 64 under HARL_GAUSS_WIDE=1 (k_gauss_head_wide, csrc/heads.hip): the plain head's
+        parameters and launches -- forward_trunk -> head_loss -> backward_trunk, the head's weight gradient from the ATL(64)
+        dhead image as for a Categorical head of 33..64 actions -- with the per-dimension log_std sums in rows of their own
+        (self.part_ls, self.ls_sum: _ensure_ws).  ReLU trunks of width 64 / 128, feed-forward or the fused 64-wide GRU."""
+        why = gauss_wide_reason(self.act_dim, self.hidden_sizes, self.activation_func, self.recurrent, self.recurrent_n)
+        if why is None and self.recurrent and self.gru_wide:  # (a 64-wide GRU sent through the composition, HARL_GRU_COMPOSED=1)
+            why = GAUSS_WIDE_REFUSALS["gru"]
+        if why is not None:
+            raise NotImplementedError(why)
+        self.gauss_wide = True
+
+    def ls_reduce(self, nblk: int, accumulate: bool) -> None:
+        """self.ls_sum = / += the fixed-order fp64 column sums of the ``nblk`` rows of self.part_ls the last loss launch wrote."""
+        call("harl_ls_reduce", ptr(self.part_ls), int(nblk), ptr(self.ls_sum), int(accumulate), stream(), tag="ls_reduce")
 
     def _init_multidiscrete(self, args: dict, action_space, init, d: int) -> None:
         """Heads in the reference's order (same RNG draws), packed first-fit IN ORDER into groups of <= 128 logits; a group is
@@ -1283,6 +1307,12 @@ class StochasticPolicy(_FlatNet):
             return nblk, False
         fx, fmask, frstd, fh = self.feat()
         Wp, bp = self._packs[-1]
+        if self.gauss_wide:  # 33..64 dimensions: no fused head gradient, the log_std sums in self.part_ls (ls_reduce)
+            call("harl_actor_head_loss_ls", ptr(fx), ptr(fmask), ptr(frstd), M, fh, ptr(Wp), ptr(bp), *self.dist_args(), ptr(idx),
+                 ptr(actions), ptr(avail), ptr(old_logp), ptr(adv), ptr(adv_moments), ptr(factor), ptr(active), clip, ent_coef, agg,
+                 mode, m_valid, m_pad, ptr(logp_out), ptr(self.dz[0]), ptr(self.dhead), ptr(self.part_scalars), None, 0,
+                 ptr(self.part_ls), s, tag="actor_head_loss")
+            return nblk, False
         dw = fuse_dw and not self.wide_head  # (heads of 33..64 actions: separate dW pass)
         call("harl_actor_head_loss", ptr(fx), ptr(fmask), ptr(frstd), M, fh, ptr(Wp), ptr(bp), *self.dist_args(), ptr(idx),
              ptr(actions), ptr(avail), ptr(old_logp), ptr(adv), ptr(adv_moments), ptr(factor), ptr(active), clip, ent_coef, agg,
@@ -1488,8 +1518,10 @@ class FusedAdam:
 
     def step(self, mode: int, const_scale: float, use_clip: bool, max_norm: float, info_out: Optional[torch.Tensor],
              logstd_off: int = -1, act_dim: int = 0, part_scalars: Optional[torch.Tensor] = None,
-             n_scalar_blocks: int = 0, scalars_hilo: Optional[torch.Tensor] = None) -> None:
+             n_scalar_blocks: int = 0, scalars_hilo: Optional[torch.Tensor] = None,
+             ls_sum: Optional[torch.Tensor] = None) -> None:
         """One fused launch: loss scalars -> scale/statistics, unfold, ||g||, clip, Adam, re-fold (harl_adam_fold).
+        ``ls_sum`` (Gaussian heads of 33..64 dimensions): the log_std gradient sums, fp64[64], instead of scalars 8.. (harl_adam_fold_ls).
         ``part_scalars``: the loss kernel's per-block partial sums, reduced inside the launch into ``net.scalars``
         (single-GPU path); ``scalars_hilo``: the all-reduced fixed-grid fp32 pieces behind the gradients in ``net.dwp_msg``
         (data-parallel path); neither = ``net.scalars`` already holds the sums."""
@@ -1498,6 +1530,16 @@ class FusedAdam:
         self.step_count += 1
         b1, b2 = g["betas"]
         n = self.net
+        if ls_sum is not None:
+            if 0 <= row < self._hyper_rows:
+                raise RuntimeError("FusedAdam.step(ls_sum=...) has no device-table form: these steps are not armed (begin_steps)")
+            call("harl_adam_fold_ls", ptr(n.flat_param), ptr(n.flat_grad), ptr(self.exp_avg), ptr(self.exp_avg_sq), n.n_params,
+                 ptr(n.dwp), ptr(n.table), n.n_entries, ptr(n.pack_arena), ptr(n.scalars), ptr(part_scalars),
+                 int(n_scalar_blocks), ptr(scalars_hilo), int(mode), float(const_scale), int(logstd_off), int(act_dim), ptr(info_out),
+                 int(use_clip), float(max_norm), float(g["lr"]), float(b1), float(b2), float(g["eps"]),
+                 float(g["weight_decay"]), 1.0 - b1 ** self.step_count, 1.0 - b2 ** self.step_count, ptr(ls_sum), ptr(self._ws),
+                 stream(), tag="adam_fold")
+            return
         if 0 <= row < self._hyper_rows:
             # armed (begin_steps): lr and the bias corrections of this step are row `row` of the device table, which is where
             # the device counter stands -- every step since begin_steps went through this launch

@@ -106,6 +106,8 @@ class OnPolicyHARunner:
         shard = (self.n_global, self.col_lo, self.col_hi) if self.comm.enabled else None
         for x in list(self.actor) + [self.critic]:
             x.comm, x.shard = self.comm, shard
+        for x in self.actor:  # (Gaussian heads of 33..64 dimensions are single-GPU: refused here, not in the first train())
+            x._refuse_gauss_wide_dp()
         # HARL_CRITIC_GROUP=1: the critic's collectives go through a communicator of their own and its update keeps its own
         # stream under data parallelism.  The group is created by the constructors (collective call: never from this lazy
         # path, where ranks may arrive at different times); without one the critic shares the actors' communicator + stream.

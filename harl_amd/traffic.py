@@ -167,6 +167,12 @@ def _actor_head_loss(a: Sequence) -> float:
                 + (4.0 * w if a[26] else 0.0) + 4.0 * H + (4.0 * 32 if (a[28] and not a[30]) else 0.0))  # dhead only when the head dW is not fused
 
 
+def _actor_head_loss_ls(a: Sequence) -> float:
+    # harl_actor_head_loss's arguments + part_ls in front of the stream: dhead is the ATL(64) image, not [M][32] rows
+    # (actions and stored log-probs are read twice, the second time from cache)
+    return _actor_head_loss(a) + a[3] * 4.0 * 32
+
+
 def _actor_head_logp(a: Sequence) -> float:
     # (xL, M, H, Whp, bhp, log_std, sx, sy, discrete, act_dim, actions, avail, logp_out, old_logp, factor, agg_mean, head_out,
     #  m_valid, m_pad, stream)
@@ -263,6 +269,7 @@ ALGORITHMIC_BYTES: Dict[str, Callable[[Sequence], float]] = {
     "harl_gru_fwd": _gru_fwd,
     "harl_gru_bwd": _gru_bwd,
     "harl_actor_head_loss": _actor_head_loss,
+    "harl_actor_head_loss_ls": _actor_head_loss_ls,
     "harl_actor_head_logp": _actor_head_logp,
     "harl_critic_head_loss": _critic_head_loss,
     "harl_update_fwd_actor": _update_fwd_actor,
@@ -403,6 +410,7 @@ ALGORITHMIC_FLOPS: Dict[str, Callable[[Sequence], float]] = {
     "harl_gru_fwd": _f_gru_fwd,
     "harl_gru_bwd": _f_gru_bwd,
     "harl_actor_head_loss": lambda a: _f_head(a[3], a[4], a[11], True) - (2.0 * a[3] * a[11] * a[4] if not a[30] else 0.0),
+    "harl_actor_head_loss_ls": lambda a: _f_head(a[3], a[4], a[11], True) - 2.0 * a[3] * a[11] * a[4],
     "harl_actor_head_logp": lambda a: _f_head(a[1], a[2], a[9], False),
     "harl_actor_head_fvp": lambda a: 0.0,
     "harl_critic_head_loss": lambda a: _f_head(a[3], a[4], 1, True),

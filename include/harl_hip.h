@@ -348,6 +348,16 @@ int harl_adam_fold_dev(float *param, float *grad, float *exp_avg, float *exp_avg
                        int n_scalar_blocks, const float *scalars_hilo, int mode, float const_scale, int logstd_off,
                        int act_dim, double *info, int use_clip, float max_norm, const double *hyper, int n_hyper_rows,
                        int *step_idx, double beta1, double beta2, float eps, float weight_decay, void *ws, void *stream);
+/* harl_adam_fold for an actor whose log_std gradient sums do not fit the scalar row -- a DiagGaussian head of 33..64 dimensions
+ * (harl_actor_head_loss_ls): grad[logstd_off + d] = ls_sum[d] (double[64], harl_ls_reduce) for d < act_dim <= 64, in the
+ * gradient norm and in the Adam update of log_std alike; every other argument and all other arithmetic is harl_adam_fold's
+ * (same kernel body; distributions.py:74-89 keeps log_std as one more parameter of the same optimiser, happo.py:89-100). */
+int harl_adam_fold_ls(float *param, float *grad, float *exp_avg, float *exp_avg_sq, long n, const float *dwp,
+                      const int *table, int n_layers, float *packs, double *scalars, const float *part_scalars,
+                      int n_scalar_blocks, const float *scalars_hilo, int mode, float const_scale, int logstd_off,
+                      int act_dim, double *info, int use_clip, float max_norm, double lr, double beta1, double beta2,
+                      float eps, float weight_decay, double bias_correction1, double bias_correction2,
+                      const double *ls_sum, void *ws, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Heads and losses.
@@ -389,6 +399,26 @@ int harl_actor_head_loss(const float *xL, const uint32_t *relu_mask, const float
                          const float *factor, const float *active, double clip_param, float entropy_coef,
                          int agg_mean, int trpo, long m_valid, long m_pad, float *logp_out, float *dzL, float *dhead,
                          float *part_scalars, float *dw_part, int n_wg, void *stream);
+/* harl_actor_head_loss for a DiagGaussian head of 33 <= act_dim <= 64 dimensions on a 64- or 128-wide last layer (Box action
+ * spaces; models/base/distributions.py:74-89, models/base/act.py:104-157 -- the same FixedNormal log-probs, entropy and
+ * sigmoid-parametrised std as the narrower heads; harl_actor_head_logp takes these heads as it is).  Same arguments and
+ * outputs, except:
+ *   discrete = 0 and dw_part = NULL are required (the fused head weight gradient stops at 32 outputs): dhead is written as
+ *   an ATL(64) image [M_pad][64], columns >= act_dim and rows that do not count exactly 0, for harl_mlp_dw_partials
+ *   (a_kind = 0, HO = 64);
+ *   part_scalars rows hold scalars 0..4 only, columns 8.. are 0: the per-dimension sums d(loss)/d(log_std_d) of workgroup b
+ *   go to part_ls[b][64] (harl_head_blocks(M) rows, columns >= act_dim 0) and are combined by harl_ls_reduce. */
+int harl_actor_head_loss_ls(const float *xL, const uint32_t *relu_mask, const float *rstd, long M, int H,
+                            const float *Whp, const float *bhp, const float *log_std, float std_x_coef,
+                            float std_y_coef, int discrete, int act_dim, const int64_t *idx, const float *actions,
+                            const float *avail, const float *old_logp, const float *adv, const double *adv_moments,
+                            const float *factor, const float *active, double clip_param, float entropy_coef,
+                            int agg_mean, int trpo, long m_valid, long m_pad, float *logp_out, float *dzL, float *dhead,
+                            float *part_scalars, float *dw_part, int n_wg, float *part_ls, void *stream);
+/* ls_sum[0..64) (double) = column sums of part_ls[n_blocks][64] in fp64 and a fixed order (no atomics): accumulate = 0
+ * overwrites ls_sum, accumulate = 1 adds to it (several minibatch segments in front of one optimiser step, as
+ * harl_reduce_scalars_set / harl_reduce_scalars do for the scalar rows). */
+int harl_ls_reduce(const float *part_ls, int n_blocks, double *ls_sum, int accumulate, void *stream);
 /* V head forward: values[M] = Whp . xL + bhp   (v_net.py:64) */
 int harl_critic_head_values(const float *xL, long M, int H, const float *Whp, const float *bhp, float *values,
                             void *stream);
