@@ -90,7 +90,7 @@ class OnPolicyBase:
         resets.  Returns the final hidden state [m, H] when ``h_last`` is set."""
         net = self.actor
         agg = int(self.action_aggregation == "mean")
-        if not reuse_trunk and net.fused_update_ok(None, train=False):  # forward + head in one launch, x_hat_2 never leaves the chip
+        if not reuse_trunk and net._step_route(True, True, train=False).kind == "fused":  # forward + head in one launch, x_hat_2 never leaves the chip
             call("harl_update_logp", *net.fused_args(obs, M), *net.dist_args(), ptr(actions), ptr(avail), ptr(logp_out),
                  ptr(old_logp), ptr(factor), agg, ptr(head_out), stream(), tag="update_logp")
             return None
@@ -266,31 +266,20 @@ class HAPPO(OnPolicyBase):
         s = stream()
         # clip, entropy coefficient, aggregation, surrogate mode: the same four in every loss launch
         loss = (float(self.clip_param), float(self.entropy_coef), int(self.action_aggregation == "mean"), self._surrogate_mode)
-        if net.fused_update_ok(idx, seq):  # fused forward + loss (csrc/update.hip), then the layer backward (hybrid) or harl_update_bwd
-            fa = net.fused_args(obs, m)
-            self._await_factor()
-            call("harl_update_fwd_actor", *fa, *net.dist_args(), ptr(actions), ptr(avail), ptr(old_logp), ptr(adv),
-                 ptr(adv_moments), ptr(factor), ptr(active), *loss, ptr(logp_out), ptr(net.dz[0]), ptr(net.part_scalars),
-                 ptr(net.part[net._part_offs[-1]:]), net.n_wg, *net.hybrid_outputs(), s, tag="update_fwd")
-            net.backward_after_fused(obs, m)
-            return net.n_wg
-        if net.fused_last_ok(idx, seq):  # deeper networks: the last hidden layer runs inside the loss launch
-            L = len(net.hidden_sizes)
-            net.forward_trunk(obs, idx, m, upto=L - 1)
-            (Wl, bl), (Wh, bh) = net._packs[L - 1], net._packs[-1]
-            self._await_factor()
-            call("harl_update_last_actor", ptr(net.xh[L - 2]), m, net.hidden_sizes[-1], ptr(Wl), ptr(bl), ptr(Wh), ptr(bh),
-                 *net.dist_args(), ptr(idx), ptr(actions), ptr(avail), ptr(old_logp), ptr(adv), ptr(adv_moments), ptr(factor),
-                 ptr(active), *loss, ptr(logp_out), ptr(net.dz[0]), ptr(net.part_scalars), ptr(net.part[net._part_offs[-1]:]),
-                 net.n_wg, s, tag="update_last")
-            net.backward_trunk(obs, idx, m, head_dw_done=True)
-            return net.n_wg
-        net.forward_trunk(obs, idx, m, seq=seq)
-        mv, mp = (seq["m"], seq["m_pad"]) if seq is not None else (0, 0)
+        route = net._step_route(idx is None, seq is None, True)
+        lead = net.step_forward(route, obs, idx, m, seq)  # the image, or the trunk as far as the route runs it in front of the loss
         self._await_factor()
-        nblk, head_dw_done = net.head_loss(m, idx, actions, avail, old_logp, adv, adv_moments, factor, active, *loss, mv, mp,
-                                           logp_out, md_ent_scale=lambda: self._md_ent_scale(idx, m, active, seq))
-        net.backward_trunk(obs, idx, m, seq=seq, head_dw_done=head_dw_done)
+        if route.kind == "layers":
+            mv, mp = (seq["m"], seq["m_pad"]) if seq is not None else (0, 0)
+            nblk, head_dw_done = net.head_loss(m, idx, actions, avail, old_logp, adv, adv_moments, factor, active, *loss, mv, mp,
+                                               logp_out, md_ent_scale=lambda: self._md_ent_scale(idx, m, active, seq))
+        else:  # the loss launches of csrc/update.hip ("last": over the rows idx gathers); both leave the head's weight gradient
+            fused = route.kind == "fused"
+            call("harl_update_fwd_actor" if fused else "harl_update_last_actor", *lead, *net.dist_args(),
+                 *(() if fused else (ptr(idx),)), ptr(actions), ptr(avail), ptr(old_logp), ptr(adv), ptr(adv_moments), ptr(factor),
+                 ptr(active), *loss, ptr(logp_out), *net.step_outputs(route), s, tag="update_fwd" if fused else "update_last")
+            nblk, head_dw_done = net.n_wg, True
+        net.step_backward(route, obs, idx, m, seq, head_dw_done)
         return nblk  # rows of part_scalars
 
     def _md_ent_scale(self, idx, m, active, seq) -> Optional[torch.Tensor]:

@@ -34,7 +34,7 @@ _FUSED_UPDATE_MODES = ("hybrid", "logp", "1", "actor", "0")
 
 
 def _fused_update_mode() -> str:
-    """``HARL_FUSED_UPDATE`` (see _FlatNet.fused_update_ok), validated: an unknown value used to behave like "1" silently."""
+    """``HARL_FUSED_UPDATE`` (see _FlatNet._step_route), validated: an unknown value used to behave like "1" silently."""
     mode = os.environ.get("HARL_FUSED_UPDATE", "hybrid")
     if mode not in _FUSED_UPDATE_MODES:
         raise ValueError(f"HARL_FUSED_UPDATE={mode!r}: expected one of {_FUSED_UPDATE_MODES}")
@@ -78,6 +78,11 @@ _ROUTES = {k: _Route(k, im) for k, im in dict(act="cached", panel="cached", trun
 # the second stream / through harl_gru_dw6;  one_wg_per_cu: every weight gradient comes out of a one-workgroup-per-CU launch
 _BwdRoute = NamedTuple("_BwdRoute", [("family", str), ("gru", str), ("hidden", str), ("fill", int), ("dw1", str),
                                      ("gates_side", bool), ("gates_dw6", bool), ("one_wg_per_cu", bool)])
+
+# _FlatNet._step_route.  kind: "fused" (the harl_update_fwd_* / harl_update_logp / harl_update_values launch) | "last" (the trunk
+# up to the last hidden layer, then harl_update_last_*) | "layers" (the whole trunk, then the head's own loss launch);  backward:
+# "layers" (backward_trunk) | "recompute" (harl_update_bwd + the combine: HARL_FUSED_UPDATE=1 / actor) | "none" (forward only)
+_StepRoute = NamedTuple("_StepRoute", [("kind", str), ("backward", str)])
 
 
 def routing_switches() -> tuple:
@@ -454,8 +459,9 @@ class _FlatNet(nn.Module):
         nwg_env = os.environ.get("HARL_NWG")
         nwg_cap = int(nwg_env) if nwg_env else max(256, min(512, n_slabs // 10))
         # ... and 256 rows when every weight gradient of this network comes out of a one-workgroup-per-CU launch (the fused forward's
-        # head gradient, harl_mlp_bwd_dx_dw for the trunk): the other 256 rows would only be cleared by them and read back by
-        # the combine (~22 MB each way per optimiser step at the 3-agent headline shapes)
+        # head gradient -- _backward_route takes _step_route's "fused" / "last" step in front of it for granted -- and
+        # harl_mlp_bwd_dx_dw for the trunk): the other 256 rows would only be cleared by them and read back by the combine
+        # (~22 MB each way per optimiser step at the 3-agent headline shapes)
         if not nwg_env and self._backward_route(M).one_wg_per_cu:
             nwg_cap = 256
         self.n_wg = max(1, min(nwg_cap, n_iter))
@@ -558,7 +564,7 @@ class _FlatNet(nn.Module):
 
     def _first_launch(self, idx_is_none: bool, partial: bool) -> _Route:
         """The launch a trunk forward starts with and what it does with self.x0n: forward_trunk dispatches on this, x0n_multi_item
-        and fused_last_ok ask it.  ``partial``: forward_trunk(upto=...), which has no whole-trunk launch.  The image does not
+        and _step_route ask it.  ``partial``: forward_trunk(upto=...), which has no whole-trunk launch.  The image does not
         depend on it ("trunk" implies wide inputs, whose other routes read the same image of X[idx]; "fused2x": identity rows
         only), so prepare_x0n in front of a captured step need not know.  Host path of every forward: comparisons only."""
         hs = self.hidden_sizes
@@ -612,7 +618,7 @@ class _FlatNet(nn.Module):
 
     def forward_trunk(self, X: torch.Tensor, idx: Optional[torch.Tensor], M: int, for_backward: bool = True,
                       seq: Optional[dict] = None, upto: Optional[int] = None) -> None:
-        """``upto``: stop after hidden layer ``upto`` (1-based; fused_last_ok: the last layer runs inside the loss launch)."""
+        """``upto``: stop after hidden layer ``upto`` (1-based; _step_route's "last": the last layer runs inside the loss launch)."""
         assert X.dim() == 2 and X.shape[1] == self.in_dim and X.is_contiguous()
         rnn_save = for_backward  # inference passes save no GRU internals (and take the latency variant of the kernel)
         if self.recurrent:
@@ -682,58 +688,70 @@ class _FlatNet(nn.Module):
         if self.recurrent:
             self.forward_rnn(seq, save=rnn_save)
 
-    # ---- fused optimiser-step path (csrc/update.hip): two equal hidden layers, inputs <= 64 wide, identity row order
-    def fused_update_ok(self, idx: Optional[torch.Tensor], seq: Optional[dict] = None, train: bool = True) -> bool:
-        """Route this pass through csrc/update.hip?  ``HARL_FUSED_UPDATE``: "hybrid" (default) = forward-only passes
-        (log-probs, factor product, values: one launch instead of two, x_hat_2 never written) AND the forward half of the
-        optimiser steps -- forward + head + loss + head gradient + dz_2 in one launch that also leaves layer 1's activation
-        record in HBM, followed by the layer-by-layer backward (x_hat_2 / mask_2 / rstd_2 never cross HBM: ~3.5 KB per
-        sample instead of ~4.5 KB, one launch less); "logp" = forward-only passes only; "1" = optimiser steps in three
-        launches with x_hat_1 recomputed in the backward (~1.9 KB per sample -- fewer bytes but more VALU work than the
-        layer kernels and slower end to end on MI355X: DESIGN.md section 3); "actor" = "1" for actors only; "0" = never."""
-        hs = self.hidden_sizes
-        mode = _fused_update_mode()
-        if self.act_id:
-            return False
-        if mode == "0" or (train and mode == "logp") or (train and mode == "actor" and isinstance(self, VNet)):
-            return False
-        if not (not self.recurrent and not self.grouped and idx is None and seq is None
-                and len(hs) == 2 and hs[0] == hs[1] and hs[0] in (64, 128) and self.in_dim <= 64 and self._layers()[-1][4] <= 8):
-            return False
-        # ... and the launch must fit the LDS of one workgroup (the ACTOR step of a 128-wide network with 33..64 inputs does not:
-        # the layer kernels take it)
-        kind = 0 if not train else (2 if isinstance(self, VNet) else 1)
-        return bool(_lib.load().harl_update_supported(self.in_dim, hs[0], self._layers()[-1][4], kind))
+    # ---- optimiser steps and forward-only passes through csrc/update.hip
+    _update_kind = 0  # ``kind`` of harl_update_supported for this class's optimiser step: 1 on StochasticPolicy, 2 on VNet
 
-    def fused_last_ok(self, idx: Optional[torch.Tensor], seq: Optional[dict] = None) -> bool:
-        """Optimiser steps of networks the two-layer launch does not cover (three or more hidden layers, wide first layers,
-        minibatches): run the LAST hidden layer inside the loss launch (harl_update_last_*: x_hat_L never written)?
-        Needs ReLU, equal 64 / 128-wide last two layers, a head of <= 8 outputs, and a layer kernel in front that stops
-        before the last layer."""
-        hs = self.hidden_sizes
-        if _fused_update_mode() != "hybrid" or self.act_id or self.recurrent or self.grouped or self.panel:
-            return False
-        if seq is not None or len(hs) < 2 or hs[-1] != hs[-2] or hs[-1] not in (64, 128) or self._layers()[-1][4] > 8:
-            return False
-        two_fused = self._first_launch(idx is None, True).kind in ("fused2x", "fused2")
-        return len(hs) >= (3 if two_fused else 2) and bool(_lib.load().harl_update_supported(0, hs[-1], self._layers()[-1][4], 2 if isinstance(self, VNet) else 1))
+    def _step_route(self, idx_is_none: bool, seq_is_none: bool, train: bool) -> _StepRoute:
+        """Which launches make up the forward and loss half of an optimiser step (``train``) or a forward-only pass (log-probs,
+        factor product, values) over rows X[idx], and which backward follows (_StepRoute above): HAPPO._forward_backward and
+        VCritic._forward_backward dispatch on this, _logp_pass and get_values ask it with (True, True, train=False).  Like
+        _first_launch it launches and allocates nothing, and it is the one reader of ``HARL_FUSED_UPDATE``: "hybrid" (default)
+        = forward-only passes in one launch instead of two (x_hat_2 never written) AND the forward half of the optimiser steps
+        -- forward + head + loss + head gradient + dz_2 in one launch that also leaves layer 1's activation record in HBM,
+        followed by the layer-by-layer backward (x_hat_2 / mask_2 / rstd_2 never cross HBM: ~3.5 KB per sample instead of
+        ~4.5 KB, one launch less), or, where that launch does not reach, the last hidden layer inside the loss launch; "logp" =
+        forward-only passes only; "1" = optimiser steps in three launches with x_hat_1 recomputed in the backward (~1.9 KB per
+        sample -- fewer bytes but more VALU work than the layer kernels and slower end to end on MI355X: DESIGN.md section
+        3); "actor" = "1" for actors only; "0" = never.
+        Both launches need ReLU, no GRU, one plain head of <= 8 outputs and equal 64 / 128-wide last two layers.  "fused" first:
+        two layers, inputs <= 64 wide, identity rows.  Then "last" (hybrid steps only): the trunk stops before the last layer,
+        so a first launch that fuses two layers needs a third -- the order keeps two-layer networks over identity rows off it."""
+        mode, hs = _fused_update_mode(), self.hidden_sizes
+        layers = _StepRoute("layers", "layers" if train else "none")
+        if (mode == "0" or self.act_id or self.recurrent or self.grouped or not seq_is_none or len(hs) < 2 or hs[-1] != hs[-2]
+                or hs[-1] not in (64, 128) or (head := self._layers()[-1][4]) > 8):
+            return layers
+        supported = _lib.load().harl_update_supported
+        step = not train or mode in ("hybrid", "1") or (mode == "actor" and self._update_kind == 1)
+        # ... and the launch must fit one workgroup's LDS (the ACTOR step of a 128-wide network with 33..64 inputs does not)
+        if (step and idx_is_none and len(hs) == 2 and self.in_dim <= 64
+                and supported(self.in_dim, hs[0], head, self._update_kind if train else 0)):
+            return _StepRoute("fused", "none" if not train else "layers" if mode == "hybrid" else "recompute")
+        if train and mode == "hybrid" and not self.panel:
+            two_fused = self._first_launch(idx_is_none, True).kind in ("fused2x", "fused2")
+            if len(hs) >= (3 if two_fused else 2) and supported(0, hs[-1], head, self._update_kind):
+                return _StepRoute("last", "layers")
+        return layers
 
-    def fused_hybrid(self) -> bool:
-        """Optimiser steps as fused forward + layer-by-layer backward (see fused_update_ok)?"""
-        return _fused_update_mode() == "hybrid"
+    def step_forward(self, route: _StepRoute, X: torch.Tensor, idx: Optional[torch.Tensor], M: int, seq: Optional[dict] = None):
+        """What the route runs in front of the loss launch -- "fused": the image (fused_args); "last": the trunk up to the last
+        hidden layer; "layers": the whole trunk -- and the leading arguments of harl_update_fwd_* / harl_update_last_*
+        ("layers": none, the head's own loss launch starts from feat())."""
+        if route.kind == "fused":
+            return self.fused_args(X, M)
+        if route.kind == "layers":
+            self.forward_trunk(X, idx, M, seq=seq)
+            return ()
+        L = len(self.hidden_sizes)
+        self.forward_trunk(X, idx, M, upto=L - 1)
+        (Wl, bl), (Wh, bh) = self._packs[L - 1], self._packs[-1]
+        return (ptr(self.xh[L - 2]), M, self.hidden_sizes[-1], ptr(Wl), ptr(bl), ptr(Wh), ptr(bh))
 
-    def hybrid_outputs(self):
-        """(xh1, rmask1, rstd1) arguments of harl_update_fwd_*: layer 1's activation record for the layer-by-layer backward
-        (hybrid), or three NULLs (harl_update_bwd recomputes it)."""
-        if not self.fused_hybrid():
-            return (None, None, None)
-        return (ptr(self.xh[0]), ptr(self.rmask[0]), ptr(self.rstd[0]))
+    def step_outputs(self, route: _StepRoute):
+        """The trailing arguments of harl_update_fwd_* / harl_update_last_*: dz of the last layer, the loss scalars' rows, the
+        head's weight-gradient partials and their rows -- and, for harl_update_fwd_*, (xh1, rmask1, rstd1): layer 1's activation
+        record for the layer-by-layer backward, or three NULLs (harl_update_bwd recomputes it)."""
+        out = (ptr(self.dz[0]), ptr(self.part_scalars), ptr(self.part[self._part_offs[-1]:]), self.n_wg)
+        if route.kind != "fused":
+            return out
+        return out + ((ptr(self.xh[0]), ptr(self.rmask[0]), ptr(self.rstd[0])) if route.backward == "layers" else (None, None, None))
 
-    def backward_after_fused(self, X: torch.Tensor, M: int) -> None:
-        if self.fused_hybrid():
-            self.backward_trunk(X, None, M, head_dw_done=True)
-        else:
+    def step_backward(self, route: _StepRoute, X: torch.Tensor, idx: Optional[torch.Tensor], M: int, seq: Optional[dict] = None,
+                      head_dw_done: bool = True) -> None:
+        if route.backward == "recompute":
             self.backward_fused(M)
+        else:
+            self.backward_trunk(X, idx, M, seq=seq, head_dw_done=head_dw_done)
 
     def fused_args(self, X: torch.Tensor, M: int):
         """(x0n, M, D, H, W1', b1', W2', b2', Wh', bh') -- the leading arguments of every harl_update_* entry point.
@@ -1124,6 +1142,7 @@ class _FlatNet(nn.Module):
 
 class StochasticPolicy(_FlatNet):
     """Actor network container (reference: models/policy_models/stochastic_policy.py:11-54)."""
+    _update_kind = 1
 
     def __init__(self, args: dict, obs_space, action_space, device: torch.device):
         obs_shape = _space_shape(obs_space)
@@ -1345,6 +1364,7 @@ class StochasticPolicy(_FlatNet):
 
 class VNet(_FlatNet):
     """Critic network container (reference: models/value_function_models/v_net.py:10-46)."""
+    _update_kind = 2
 
     def __init__(self, args: dict, cent_obs_space, device: torch.device):
         shape = _space_shape(cent_obs_space)

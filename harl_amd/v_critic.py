@@ -73,7 +73,7 @@ class VCritic:
         net.fold()
         Wp, bp = net._packs[-1]
         out = torch.empty(M, 1, **self.tpdv)
-        if net.fused_update_ok(None, train=False):
+        if net._step_route(True, True, train=False).kind == "fused":
             call("harl_update_values", *net.fused_args(x, M), ptr(out), stream(), tag="update_values")
             return out, (None if rnn_states_critic is None else _as_dev(rnn_states_critic, self.device))
         if not net.recurrent:
@@ -152,32 +152,24 @@ class VCritic:
 
     def _forward_backward(self, net, share_obs, idx, m, value_preds, returns, vn, seq, s) -> None:
         """Forward, value loss and backward of one minibatch: the unscaled folded gradients and the loss kernel's partial sums."""
-        if m > 0 and net.fused_update_ok(idx, seq):  # fused forward + loss (csrc/update.hip), then the layer backward (hybrid) or harl_update_bwd
-            call("harl_update_fwd_critic", *net.fused_args(share_obs, m), ptr(value_preds), ptr(returns),
-                 ptr(vn.stats) if vn is not None else None, float(self.clip_param), int(self.use_clipped_value_loss),
-                 int(self.use_huber_loss), float(self.huber_delta), ptr(net.dz[0]), ptr(net.part_scalars),
-                 ptr(net.part[net._part_offs[-1]:]), net.n_wg, *net.hybrid_outputs(), s, tag="update_fwd_critic")
-            net.backward_after_fused(share_obs, m)
-        elif m > 0 and net.fused_last_ok(idx, seq):  # deeper networks: the last hidden layer runs inside the loss launch
-            L = len(net.hidden_sizes)
-            net.forward_trunk(share_obs, idx, m, upto=L - 1)
-            (Wl, bl), (Wh, bh) = net._packs[L - 1], net._packs[-1]
-            call("harl_update_last_critic", ptr(net.xh[L - 2]), m, net.hidden_sizes[-1], ptr(Wl), ptr(bl), ptr(Wh), ptr(bh),
-                 ptr(idx), ptr(value_preds), ptr(returns), ptr(vn.stats) if vn is not None else None, float(self.clip_param),
-                 int(self.use_clipped_value_loss), int(self.use_huber_loss), float(self.huber_delta), ptr(net.dz[0]),
-                 ptr(net.part_scalars), ptr(net.part[net._part_offs[-1]:]), net.n_wg, s, tag="update_last_critic")
-            net.backward_trunk(share_obs, idx, m, head_dw_done=True)
-        elif m > 0:
-            net.forward_trunk(share_obs, idx, m, seq=seq)
+        if m <= 0:  # an empty data-parallel shard launches nothing
+            return
+        route = net._step_route(idx is None, seq is None, True)
+        lead = net.step_forward(route, share_obs, idx, m, seq)  # the image, or the trunk as far as the route runs it in front of the loss
+        loss = (ptr(value_preds), ptr(returns), ptr(vn.stats) if vn is not None else None, float(self.clip_param),
+                int(self.use_clipped_value_loss), int(self.use_huber_loss), float(self.huber_delta))
+        if route.kind == "layers":
             Wp, bp = net._packs[-1]
             fx, fmask, frstd, fh = net.feat()
             mv, mp = (seq["m"], seq["m_pad"]) if seq is not None else (0, 0)
-            call("harl_critic_head_loss", ptr(fx), ptr(fmask), ptr(frstd), m, fh,
-                 ptr(Wp), ptr(bp), ptr(idx), ptr(value_preds), ptr(returns), ptr(vn.stats) if vn is not None else None,
-                 float(self.clip_param), int(self.use_clipped_value_loss), int(self.use_huber_loss), float(self.huber_delta),
-                 mv, mp, ptr(net.dz[0]), ptr(net.dhead), ptr(net.part_scalars), ptr(net.part[net._part_offs[-1]:]),
-                 net.n_wg, s, tag="critic_head_loss")  # head weight gradient fused into this launch
-            net.backward_trunk(share_obs, idx, m, seq=seq, head_dw_done=True)
+            call("harl_critic_head_loss", ptr(fx), ptr(fmask), ptr(frstd), m, fh, ptr(Wp), ptr(bp), ptr(idx), *loss, mv, mp,
+                 ptr(net.dz[0]), ptr(net.dhead), ptr(net.part_scalars), ptr(net.part[net._part_offs[-1]:]), net.n_wg, s,
+                 tag="critic_head_loss")
+        else:  # the loss launches of csrc/update.hip ("last": over the rows idx gathers)
+            fused = route.kind == "fused"
+            call("harl_update_fwd_critic" if fused else "harl_update_last_critic", *lead, *(() if fused else (ptr(idx),)), *loss,
+                 *net.step_outputs(route), s, tag="update_fwd_critic" if fused else "update_last_critic")
+        net.step_backward(route, share_obs, idx, m, seq)  # (every one of the three launches leaves the head's weight gradient)
 
     def update(self, sample, value_normalizer=None):
         """API-compatible single update on a gathered minibatch (v_critic.py:116-157)."""

@@ -1,4 +1,4 @@
-"""Routing of the optimiser steps (nets.fused_update_ok / fused_last_ok), host side without a GPU: the launch sequence of a whole
+"""Routing of the optimiser steps (nets._FlatNet._step_route), host side without a GPU: the launch sequence of a whole
 train() with the C-ABI calls recorded instead of executed."""
 import numpy as np
 import pytest

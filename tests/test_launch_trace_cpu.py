@@ -6,7 +6,9 @@ the backward (nets._FlatNet._backward_route; configurations 15 and up were recor
 BACKWARD_REACHES names what each configuration must go on launching.  Configurations 33 and up were recorded before an action
 head's launches moved into nets.StochasticPolicy -- the heads of a train() no earlier configuration has, and the second kind of
 configuration (LT.ACTOR_CONFIGS: the rollout entry points, update() on a gathered sample, the pieces of HATRPO's update):
-HEAD_REACHES names the head launch each of them must go on reaching."""
+HEAD_REACHES names the head launch each of them must go on reaching.  Configurations 60 and up, and 46, were recorded before
+the route of an optimiser step was decided in one place (nets._FlatNet._step_route) -- the values of HARL_FUSED_UPDATE, the
+callers and the row orders nothing earlier takes: STEP_REACHES names the loss launch each must go on reaching."""
 import importlib.util
 import json
 import os
@@ -40,6 +42,13 @@ def test_launch_traces_equal_the_recorded_ones(stub_kernels, monkeypatch):  # no
         asked.add((r.kind, r.image, idx_is_none, partial))
         return r
     monkeypatch.setattr(_FlatNet, "_first_launch", spy)
+    steps, step_route = set(), _FlatNet._step_route
+
+    def step_spy(self, idx_is_none, seq_is_none, train):
+        r = step_route(self, idx_is_none, seq_is_none, train)
+        steps.add((r.kind, r.backward, idx_is_none, seq_is_none, train, type(self).__name__))
+        return r
+    monkeypatch.setattr(_FlatNet, "_step_route", step_spy)
     got = LT.normalise({k: LT.run_config(k, monkeypatch) for k in (*LT.CONFIGS, *LT.ACTOR_CONFIGS)})
     diff = LT.compare(want, got)
     assert not diff, "\n".join(diff)
@@ -52,11 +61,20 @@ def test_launch_traces_equal_the_recorded_ones(stub_kernels, monkeypatch):  # no
                                       ("fused2x", "cached_identity"), ("fused2", "clobbers"), ("input", "clobbers")}
     # ... and every route of the backward (nets._backward_route) and every head launch (HEAD_REACHES): each configuration
     # recorded for one still launches it
-    for name, reaches in (*BACKWARD_REACHES.items(), *HEAD_REACHES.items()):
+    for name, reaches in (*BACKWARD_REACHES.items(), *HEAD_REACHES.items(), *STEP_REACHES.items()):
         for r in reaches:
             entry_tag, pred = (r, None) if isinstance(r, str) else r
             hits = _launches(got[name], entry_tag)
             assert hits and (pred is None or any(pred(a) for a in hits)), (name, entry_tag)
+    # ... and every route of an optimiser step (nets._step_route): by what the route function answered -- each (kind, backward)
+    # pair that exists, both values of each argument, both network classes -- and by the loss launches a configuration stays off
+    assert {s[:2] for s in steps} == {("fused", "layers"), ("fused", "recompute"), ("fused", "none"), ("last", "layers"),
+                                      ("layers", "layers"), ("layers", "none")}
+    assert all({s[i] for s in steps} == {True, False} for i in (2, 3, 4))
+    assert {s[5] for s in steps if s[0] != "layers"} == {s[5] for s in steps if s[0] == "layers"} == {"StochasticPolicy", "VNet"}
+    for name, off in STEP_AVOIDS.items():
+        hit = {c[0] for c in got[name] if c[0].startswith(off)}
+        assert not hit, (name, hit)
     assert not _launches(got["16_h128x2_obs40_bwd_fused"], "harl_mlp_bwd_dx_dw:bwd_full")       # 64-wide image: the layer kernels
     assert not _launches(got["16_h128x2_obs40_bwd_fused"], "harl_mlp_bwd_dx_dw:bwd_full_dw1")
     assert not _launches(got["22_gru64_dw6"], "harl_mlp_dw_partials_multi:dw_gru")
@@ -159,6 +177,7 @@ HEAD_REACHES = {
                             ("harl_mlp_dw_partials:dw_head", lambda a: a[3] == 64),                   # ... the separate dW pass
                             ("harl_actor_head_logp:actor_head_logp", lambda a: (a[17], a[18]) == (0, 0)), "harl_update_values:update_values"],
     "45_haa2c_box": [("harl_update_fwd_actor:update_fwd", lambda a: a[25] == 2), "harl_update_logp:update_logp"],
+    "46_happo_box_logp": [("harl_actor_head_loss:actor_head_loss", lambda a: a[30] is not None and a[23] == 0)],  # (its passes: STEP_REACHES)
     "50_hatrpo_box": _HATRPO_PLAIN + ["harl_update_logp:update_logp"],
     "51_hatrpo_h64_discrete5": _HATRPO_PLAIN + [("harl_actor_head_fvp:actor_head_fvp", lambda a: a[13] == 1 and a[15] is not None)],
     "52_hatrpo_gru64_box": _HATRPO_PLAIN + ["harl_gru_tangent:gru_tangent", ("harl_actor_head_fvp:actor_head_fvp", _padded(16, 17)),
@@ -169,6 +188,51 @@ HEAD_REACHES = {
                                                   ("harl_cat_head_logp:cat_head_logp", _padded(13, 14))],
     "56_hatrpo_h256_box": _HATRPO_PLAIN + ["harl_head_dw_rows256:dw_head", "harl_mlp_panel_tangent:tangent_panel"],
     "57_hatrpo_tanh_box": _HATRPO_PLAIN + ["harl_act_ln_tangent:act_ln_tangent"],
+}
+
+
+# configuration -> the loss launches (and the launches that follow from the same route) its optimiser steps and forward-only
+# passes were recorded to reach, as in BACKWARD_REACHES, with a predicate where an argument carries the route.  Argument
+# positions as in include/harl_hip.h: harl_update_fwd_actor(x0n, M, D, H [3], .., xh1 [31], rmask1, rstd1),
+# harl_update_fwd_critic(x0n, M, D, H [3], .., xh1 [21], ..), harl_update_last_actor(x, M, H [2], .., idx [12], ..),
+# harl_update_last_critic(x, M, H [2], .., idx [7], ..)
+_FWD_A, _FWD_C = "harl_update_fwd_actor:update_fwd", "harl_update_fwd_critic:update_fwd_critic"
+_LAST_A, _LAST_C = "harl_update_last_actor:update_last", "harl_update_last_critic:update_last_critic"
+_LOSS_A, _LOSS_C = "harl_actor_head_loss:actor_head_loss", "harl_critic_head_loss:critic_head_loss"
+_LOGP, _HEAD_LOGP = "harl_update_logp:update_logp", "harl_actor_head_logp:actor_head_logp"
+_HYBRID = [(_FWD_A, lambda a: a[31] is not None and a[32] is not None and a[33] is not None),  # layer 1's activation record
+           (_FWD_C, lambda a: a[21] is not None and a[22] is not None and a[23] is not None)]
+STEP_REACHES = {
+    "01_h128x2": _HYBRID + [_LOGP],
+    "02_h128x2_obs40": [_LOSS_A, _LOGP, (_FWD_C, lambda a: a[2] == 60 and a[21] is not None)],  # the ACTOR step does not fit the LDS
+    "03_h128x3": [(_LAST_A, lambda a: a[12] is None and a[2] == 128), (_LAST_C, lambda a: a[7] is None), _HEAD_LOGP],
+    "04_h128x3_mb2": [(_LAST_A, lambda a: a[12] is not None), (_LAST_C, lambda a: a[7] is not None)],
+    "05_h128_64": [_LOSS_A, _LOSS_C, _HEAD_LOGP],
+    "14a_h128x2_logp": [_LOSS_A, _LOSS_C, _LOGP],
+    "20_h128x2_fused1": [(_FWD_A, lambda a: a[31] is None and a[32] is None and a[33] is None),  # "recompute": nothing to leave
+                         (_FWD_C, lambda a: a[21] is None and a[22] is None and a[23] is None), "harl_update_bwd:update_bwd", _LOGP],
+    "60_mappo_share": _HYBRID,
+    "61_mappo_share_mb2": [(_LOSS_A, lambda a: a[12] is not None), _LOSS_C],  # gathered rows (idx [12]): the layer kernels
+    "62_h128x2_fused_actor": [(_FWD_A, lambda a: a[31] is None), "harl_update_bwd:update_bwd", _LOSS_C, _LOGP],
+    "63_h128x2_fused0": [_LOSS_A, _LOSS_C, _HEAD_LOGP],
+    "64_h128x2_mb2": [_LOSS_A, _LOSS_C, _LOGP],  # two layers, both fused by the first launch: nothing left for "last"
+    "65_h128x2_obs40_mb2": [(_LAST_A, lambda a: a[12] is not None and a[2] == 128), (_LAST_C, lambda a: a[7] is not None), _LOGP],
+    "66_h128x3_fused1": [_LOSS_A, _LOSS_C, _HEAD_LOGP],
+    "67_h64x2": [(_FWD_A, lambda a: a[3] == 64 and a[31] is not None), (_FWD_C, lambda a: a[3] == 64 and a[21] is not None), _LOGP],
+    "68_h128x2_act12": [_LOSS_A, _HEAD_LOGP, (_FWD_C, lambda a: a[21] is not None)],  # a head of more than 8 outputs
+    "46_happo_box_logp": [_LOSS_A, _LOGP, "harl_update_values:update_values"],
+}
+# ... and the entry points (by prefix) none of its launches may start with
+STEP_AVOIDS = {
+    "14a_h128x2_logp": ("harl_update_fwd", "harl_update_last", "harl_update_bwd"),
+    "20_h128x2_fused1": ("harl_mlp_bwd_dx", "harl_update_last"),
+    "61_mappo_share_mb2": ("harl_update_fwd", "harl_update_last", "harl_update_bwd"),
+    "62_h128x2_fused_actor": ("harl_update_fwd_critic", "harl_update_last"),
+    "63_h128x2_fused0": ("harl_update_",),
+    "64_h128x2_mb2": ("harl_update_fwd", "harl_update_last", "harl_update_bwd"),
+    "65_h128x2_obs40_mb2": ("harl_update_fwd", "harl_update_bwd", "harl_actor_head_loss", "harl_critic_head_loss"),
+    "66_h128x3_fused1": ("harl_update_",),
+    "68_h128x2_act12": ("harl_update_fwd_actor", "harl_update_last", "harl_update_logp"),
 }
 
 
@@ -206,10 +270,11 @@ def test_prepare_x0n_leaves_nothing_to_build(stub_kernels, monkeypatch):  # noqa
     calls, seen = stub_kernels, dict(built=0, dropped=0, partial=0, fused_args=0)
     for label, net, X, idx, seq in _cases(monkeypatch):
         forwards = [lambda: net.forward_trunk(X, idx, M, seq=seq)]
-        if net.fused_last_ok(idx, seq):
+        kind = net._step_route(idx is None, seq is None, True).kind
+        if kind == "last":
             seen["partial"] += 1
             forwards.append(lambda: net.forward_trunk(X, idx, M, upto=len(net.hidden_sizes) - 1))
-        if net.fused_update_ok(idx, seq):
+        if kind == "fused":
             seen["fused_args"] += 1
             forwards.append(lambda: net.fused_args(X, M))
         for fwd in forwards:

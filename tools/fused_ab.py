@@ -82,11 +82,11 @@ def ab(rows: int, reps: int, discrete: bool = False):
         for _ in range(reps):
             net._ensure_ws(rows)
             s = _lib.stream()
-            if net.fused_update_ok(None):
-                _lib.call("harl_update_fwd_critic", *net.fused_args(so, rows), _lib.ptr(vp), _lib.ptr(ret), None, 0.2, 1, 1, 10.0,
-                          _lib.ptr(net.dz[0]), _lib.ptr(net.part_scalars), _lib.ptr(net.part[net._part_offs[-1]:]), net.n_wg,
-                          *net.hybrid_outputs(), s, tag="update_fwd_critic")
-                net.backward_after_fused(so, rows)
+            route = net._step_route(True, True, True)
+            if route.kind == "fused":
+                _lib.call("harl_update_fwd_critic", *net.step_forward(route, so, None, rows), _lib.ptr(vp), _lib.ptr(ret), None, 0.2, 1,
+                          1, 10.0, *net.step_outputs(route), s, tag="update_fwd_critic")
+                net.step_backward(route, so, None, rows)
             else:
                 net.forward_trunk(so, None, rows)
                 Wp, bp = net._packs[-1]

@@ -70,6 +70,18 @@ CONFIGS = {
     "33_md_train": ([128, 128], dict(nvec=(41, 41, 41, 30)), {}),
     "34_gru64_discrete100": ([64, 64], dict(_GRU, discrete=100), {}),
     "35_haa2c": ([128, 128], dict(algo="haa2c", a2c_epoch=2), {}),
+    # ... and the optimiser-step routes (nets._FlatNet._step_route) nothing above takes: the shared actor of MAPPO as the caller,
+    # HARL_FUSED_UPDATE=actor and =0, gathered rows on a two-layer network (19 inputs: the layer kernels; 40 / 60: the last layer
+    # inside the loss launch), =1 on a network the one-launch step does not cover, that step at width 64, a head of more than 8 outputs
+    "60_mappo_share": ([128, 128], dict(algo="mappo", share_param=True), {}),
+    "61_mappo_share_mb2": ([128, 128], dict(algo="mappo", share_param=True, actor_num_mini_batch=2, critic_num_mini_batch=2), {}),
+    "62_h128x2_fused_actor": ([128, 128], {}, dict(HARL_FUSED_UPDATE="actor")),
+    "63_h128x2_fused0": ([128, 128], {}, dict(HARL_FUSED_UPDATE="0")),
+    "64_h128x2_mb2": ([128, 128], dict(actor_num_mini_batch=2, critic_num_mini_batch=2), {}),
+    "65_h128x2_obs40_mb2": ([128, 128], dict(obs=40, sobs=60, actor_num_mini_batch=2, critic_num_mini_batch=2), {}),
+    "66_h128x3_fused1": ([128, 128, 128], {}, dict(HARL_FUSED_UPDATE="1")),
+    "67_h64x2": ([64, 64], {}, {}),
+    "68_h128x2_act12": ([128, 128], dict(act=12), {}),
 }
 _TRPO = dict(kl_threshold=0.01, ls_step=10, accept_ratio=0.5, backtrack_coeff=0.8)
 _REC = dict(use_recurrent_policy=True)
@@ -84,6 +96,7 @@ ACTOR_CONFIGS = {
     "43_happo_gru64_discrete200": ("HAPPO", [64], ("Discrete", 200), _REC, {}),
     "44_happo_discrete64": ("HAPPO", [128, 128], ("Discrete", 64), {}, {}),
     "45_haa2c_box": ("HAA2C", [128, 128], ("Box", 3), dict(a2c_epoch=2), {}),
+    "46_happo_box_logp": ("HAPPO", [128, 128], ("Box", 3), {}, dict(HARL_FUSED_UPDATE="logp")),  # a layer-kernel step, fused get_values
     "50_hatrpo_box": ("HATRPO", [128, 128], ("Box", 3), {}, {}),
     "51_hatrpo_h64_discrete5": ("HATRPO", [64, 64], ("Discrete", 5), {}, {}),
     "52_hatrpo_gru64_box": ("HATRPO", [64, 64], ("Box", 3), _REC, {}),
