@@ -86,7 +86,8 @@ def _runner_class(base_cls, ours):
         # update-side state the reference constructor knows nothing about (communicator, column shard, scratch)
         _init_update_state = ours._init_update_state
         _ensure_update_state = ours._ensure_update_state
-        _critic_first_ok = getattr(ours, "_critic_first_ok", None)
+        CRITIC_STREAM_MAX_ROWS = ours.CRITIC_STREAM_MAX_ROWS
+        _train_schedule = ours._train_schedule
         _prepare_inputs = ours._prepare_inputs
         _fp_normalised_advantages = ours._fp_normalised_advantages
         _check_comms = ours._check_comms

@@ -7,13 +7,14 @@ objects directly from the spaces, which is also what ``bench.py`` and the tests 
 """
 from __future__ import annotations
 
+import contextlib
 import os
-from typing import List, Optional
+from typing import List, NamedTuple, Optional
 
 import torch
 
 from . import _lib
-from .buffers import OnPolicyActorBuffer, OnPolicyCriticBufferEP, OnPolicyCriticBufferFP, rng_sync
+from .buffers import OnPolicyActorBuffer, OnPolicyCriticBufferEP, OnPolicyCriticBufferFP, consume_randperm, rng_sync
 from ._lib import call, ptr, stream
 from .dist import Comm, shard_columns
 from .happo import HAA2C, HAPPO
@@ -23,6 +24,78 @@ from .v_critic import VCritic
 from .valuenorm import ValueNorm
 
 ALGO_REGISTRY = {"happo": HAPPO, "hatrpo": HATRPO, "haa2c": HAA2C, "mappo": MAPPO}
+
+
+class _TrainSchedule(NamedTuple):
+    """The stream schedule of one OnPolicyHARunner.train() call (decided by _train_schedule, where the reasons are)."""
+    critic: str          # "first" | "staggered" | "last"
+    critic_stream: bool  # the critic's launches go to a stream of their own ("staggered": always; "last": never)
+    side: bool           # pre-update log-prob passes that the first forward cannot supply go to the side stream
+    side_ahead: bool     # ... one agent ahead of the main stream instead of all up front
+    post_stream: bool    # a recurrent agent's post-update pass goes to its own stream when the next agent can await it
+    last_post: bool      # the pass behind the last agent of the order runs too
+
+
+def _stream(runner, name: str):
+    """The runner's stream ``name`` (``_critic_stream``, ``_side_stream``, ``_post_stream``): created at first use, then kept."""
+    if getattr(runner, name, None) is None:
+        setattr(runner, name, torch.cuda.Stream(device=runner.device))
+    return getattr(runner, name)
+
+
+def _on(s):
+    """Context in which launches go to stream ``s``; None: they stay on the current one (and nothing of torch.cuda is touched)."""
+    return contextlib.nullcontext() if s is None else torch.cuda.stream(s)
+
+
+class _StaggeredCritic:
+    """The critic's update handed out one epoch at a time next to the actors' (_train_schedule, "staggered").  The global CPU
+    generator keeps TWO positions: the actors', which is the generator's own between two epochs, and the critic's, kept here.
+    Built at the actors' position: the critic's starts behind ``footprint``, the sizes of every draw the actors will take
+    (the generator advance of torch.randperm(n) each, no permutation materialised), and the generator is left where it was.
+    ``epochs``: VCritic._train_epochs, ``n_epochs`` of them; ``stream``: where they are enqueued (None: where the caller is)."""
+
+    def __init__(self, epochs, n_epochs: int, footprint, stream):
+        self.gen, self.left, self.stream = epochs, n_epochs, stream
+        rng_sync()
+        actor_state = torch.get_rng_state()
+        for n in footprint:
+            consume_randperm(n)
+        rng_sync()
+        self.start = self.state = torch.get_rng_state()
+        torch.set_rng_state(actor_state)
+
+    def epoch(self, after_event=None) -> None:
+        """The next epoch (if one is left), ordered behind ``after_event``, drawn from the critic's position; the generator is
+        back at the actors' position afterwards, also when the epoch raises."""
+        if self.left <= 0:
+            return
+        rng_sync()
+        actor_state = torch.get_rng_state()
+        torch.set_rng_state(self.state)
+        try:
+            if after_event is not None:
+                self.stream.wait_event(after_event)
+            with _on(self.stream):
+                next(self.gen)
+            self.left -= 1
+            rng_sync()
+            self.state = torch.get_rng_state()
+        finally:
+            rng_sync()  # (the deferred advances of an epoch that raised are the critic's too)
+            torch.set_rng_state(actor_state)
+
+    def finish(self) -> None:
+        """Behind the last actor: the actors must have drawn exactly the footprint; then the epochs not handed out yet.
+        ``state`` is then what the in-order run leaves the generator in."""
+        rng_sync()
+        if not torch.equal(torch.get_rng_state(), self.start):
+            raise RuntimeError("the actors' draws from the CPU generator are not what rng_footprint() announced: the staggered "
+                               "critic's permutations were not drawn from the state the in-order update's critic finds")
+        while self.left > 0:
+            self.epoch()
+        for _ in self.gen:  # (run the generator to its end)
+            pass
 
 
 class OnPolicyHARunner:
@@ -141,6 +214,84 @@ class OnPolicyHARunner:
                                                    cb.masks[-1].reshape(rows, 1))
         cb.compute_returns(next_value, self.value_normalizer)
 
+    def _train_schedule(self, fast, B: int, on_gpu: bool) -> _TrainSchedule:
+        """Where one train() call puts the critic's update and the actors' log-prob passes (``fast``: per actor, whether it
+        has ``masked_moments``; ``B``: rows per minibatch of a full-buffer update; ``on_gpu``: the device is a GPU).  The only
+        reader of the seven switches, at every call: bench.py and the tests flip them between the train() calls of one process.
+        Everything here is known before the host waits for the active-entry counts.
+
+        ``critic`` "first": the critic update may be enqueued before the actors'.  Only when nothing in train() materialises a
+        permutation (one full-buffer minibatch everywhere, feed-forward nets, HAPPO-family actors): then every sampler merely
+        advances the CPU generator by a count, the final generator state does not depend on the order of those advances, and the
+        critic reads nothing the actors write.  Its kernels are enqueued BEFORE the host waits on the event behind the counts'
+        copy: the GPU works through them while the host queues the first actor's launches instead of idling behind a drained
+        stream.  HARL_CRITIC_FIRST=0: not first.
+        ``critic_stream`` with "first": ... and on a stream of its own (single-GPU runs): the critic's twenty-odd launches are
+        independent of the actors', and every one of these persistent kernels ends with a tail in which most CUs have run out of
+        slabs (kernel time 0.19-0.26 ms against 0.14-0.20 ms for a wave's own slab loop, tools/phase_cycles.py) -- the other
+        chain's next kernel fills it.  HARL_CRITIC_STREAM=0 keeps one stream.
+        Under data parallelism the second stream needs the critic's own communicator (two chains issuing into ONE
+        communicator would have to interleave their collectives identically on every rank).
+        Round 6, session 3: ... and only where the launches are short.  From ~150 000 rows per minibatch every heavy kernel
+        of either chain fills the chip for 0.2 - 0.5 ms (one workgroup per CU, LDS-bound occupancy): the other chain's light
+        kernels then wait for a whole heavy launch to drain, the sum of the kernel times is the update either way, and
+        one stream measured as fast or faster (16.06 against 16.18 ms at 4096 threads, 8.90 / 9.00 at 2048, 5.45 / 5.58 at
+        1024 -- and 3.90 against 3.73 at 512 threads, where the second stream stays; profiles/r06s3_critic_stream_ab.md).
+        HARL_CRITIC_STREAM=1 forces the second stream, 0 forbids it; any other value is the size rule.
+
+        ``critic`` "staggered" (always on its own stream), round 6: the critic's update NEXT TO the actors' also where
+        permutations are materialised (recurrent policies, several minibatches).  In the reference the critic's samplers draw from
+        the global CPU generator AFTER every actor's, so the generator is fast-forwarded over the actors' draws first (their sizes
+        are known: HAPPO.rng_footprint; agents without an active entry draw nothing, happo.py:119-120), the critic's train() -- on
+        a stream of its own -- takes its permutations from exactly the state the reference's critic finds, and the generator goes
+        back to where the actors start; at the end it is set to the state behind the critic's draws (_StaggeredCritic).  Every
+        permutation and the final state are bit-identical to the in-order run.  What it buys: with GRU policies the main stream
+        idles ~0.4 ms per agent behind the previous agent's post-update log-prob pass (a full-length chain on 6 % of the chip:
+        3.9 of the SMAC update's 29.5 ms, rocprofv3 trace of round 6, profiles/r06_smac_timeline.md) and then ran the critic's
+        2.4 ms at the very end; now the critic's launches fill those gaps.
+        ... one EPOCH at a time (VCritic._train_epochs), epoch k enqueued right behind agent k's update and ordered behind
+        its event: that is where the main stream goes idle (agent k + 1's loss waits for agent k's post-update pass); run
+        all at once up front the critic only competed with the first agent's kernels (27.7 against 28.3 ms, SMAC 3s5z).
+        HARL_CRITIC_STREAM=0 or HARL_CRITIC_EARLY=0: ``critic`` "last", after the actors on the main stream, the reference's order.
+
+        ``side``: pre-update log-probs that cannot come out of the first epoch's forward (recurrent policies: full-length unroll
+        from rnn_states[0]; several minibatches; which agents those are depends on the counts: train()'s ``fused_old``) depend
+        only on the agent's OWN pre-update weights, not on the agents before it (on_policy_ha_runner.py:66-83) -- so they are
+        enqueued on a side stream, where the long, narrow recurrences (N/32 dependent chains of T steps) run next to the update
+        kernels of the agents in front instead of in series with them; agent k's update waits for event k.  HARL_SIDE_STREAM=0:
+        on the main stream, in front of each agent's update.  (Not a question of the device: the tests' recorder on device "cpu"
+        sets HARL_SIDE_STREAM=0.)
+        ``side_ahead``: ... ONE AGENT AHEAD of the main stream (round 6, second session): enqueueing all of them up front is ~0.3
+        ms of host time each -- the raw rocprofv3 trace of the 8-agent recurrent update showed the main queue EMPTY for the first
+        2.6 of its 22.7 ms while the host was still feeding the side stream.  The first agent's pass goes out up front, agent
+        k + 1's right behind the launches of agent k's update (2.5 ms of queued GPU work for a 0.47 ms pass): same kernels, same
+        operands per agent.  HARL_SIDE_AHEAD=0: all up front, as before.
+
+        ``post_stream``: post-update log-probs of RECURRENT policies (full-length unroll: N/32 dependent chains of T steps, ~0.5 ms
+        on 32 waves of the chip at the SMAC sizes) go to a stream of their own when the next agent can await them: the next
+        agent's first forward -- sequence tables, input image, MLP layers, the training GRU forward -- needs nothing from them;
+        only its first LOSS launch consumes the factor and waits for the event (HAPPO._await_factor).  Same kernels, same
+        operands, same order per tensor: bit-identical results.  HARL_POST_STREAM=0 keeps the pass on the main stream.
+        ``last_post``: the factor behind the LAST agent of the order is handed to nobody (on_policy_ha_runner.py:96-124 computes
+        it and drops it): no clone, no forward over the whole batch.  HARL_LAST_POST_PASS=1 runs it all the same (device "cpu"
+        exists under the tests' launch recorder only, which pins the reference's one pass per agent)."""
+        env = os.environ.get
+        cs_mode = env("HARL_CRITIC_STREAM", "auto")
+        own_comm = not self.comm.enabled or self.critic.comm is not self.comm
+        if (all(fast) and env("HARL_CRITIC_FIRST", "1") != "0" and self.critic.one_full_minibatch()
+                and all(hasattr(a, "fuses_old_logp") and a.fuses_old_logp() for a in self.actor)):
+            critic, critic_stream = "first", bool(on_gpu and own_comm and cs_mode != "0"
+                                                  and (cs_mode == "1" or B <= self.CRITIC_STREAM_MAX_ROWS))
+        elif (on_gpu and all(hasattr(a, "rng_footprint") for a in self.actor) and own_comm
+              and cs_mode != "0" and env("HARL_CRITIC_EARLY", "1") != "0"):
+            critic, critic_stream = "staggered", True
+        else:
+            critic, critic_stream = "last", False
+        return _TrainSchedule(critic, critic_stream, side=env("HARL_SIDE_STREAM", "1") != "0",
+                              side_ahead=env("HARL_SIDE_AHEAD", "1") != "0",
+                              post_stream=on_gpu and env("HARL_POST_STREAM", "1") != "0",
+                              last_post=env("HARL_LAST_POST_PASS", "0") == "1" or not on_gpu)
+
     # ---- on_policy_ha_runner.py:11-130 ------------------------------------------------------------
     @torch.no_grad()
     def train(self):
@@ -149,6 +300,8 @@ class OnPolicyHARunner:
         N = self.col_hi - self.col_lo
         B = T * N
         dev = self.device
+        on_gpu = dev.type == "cuda"
+        main = torch.cuda.current_stream(dev) if on_gpu else None
         actor_train_infos = []
         for x in self.actor:  # cached normalised-input images never outlive one update (nets.invalidate_caches)
             x.actor.invalidate_caches()
@@ -162,7 +315,7 @@ class OnPolicyHARunner:
         else:
             rng_sync()
             agent_order = [int(a) for a in torch.randperm(self.num_agents).numpy()]  # first CPU-RNG draw of train()
-        # Host syncs per train(): ONE read-back of every agent's active-entry count up front (early-out test,
+        # ---- moments.  Host syncs per train(): ONE read-back of every agent's active-entry count up front (early-out test,
         # happo.py:119-120) and ONE of all training statistics at the end; nothing in between waits for the GPU.
         fast = [hasattr(a, "masked_moments") for a in self.actor]
         mom_all = torch.zeros(self.num_agents, 3, dtype=torch.float64, device=dev)
@@ -171,223 +324,137 @@ class OnPolicyHARunner:
                 adv_a = advantages if self.state_type == "EP" else advantages[:, :, a].contiguous()
                 self.actor[a].masked_moments(self.actor_buffer[a], adv_a, mom_all[a])
         self.comm.all_reduce_sum(mom_all)
-        # The only mid-train host read: the active-entry counts (early-out test).  It is an asynchronous copy into pinned
-        # memory followed by an event; when the critic update may run first (it is independent of the actors, and with one
-        # full-buffer minibatch everywhere no permutation is ever materialised, so the CPU generator only advances by
-        # counts that do not depend on the order) its kernels are enqueued BEFORE the host waits on that event: the GPU
-        # works through them while the host queues the first actor's launches instead of idling behind a drained stream.
+        # The only mid-train host read: the active-entry counts, an asynchronous copy into pinned memory followed by an event
         if self._counts_host is None or self._counts_host.numel() != self.num_agents:
             self._counts_host = torch.empty(self.num_agents, dtype=torch.float64, pin_memory=torch.cuda.is_available())
         self._counts_host.copy_(mom_all[:, 2], non_blocking=True)
         ev = torch.cuda.Event()
         ev.record()
-        cinfo, critic_done = None, None
-        if self._critic_first_ok(fast):
-            # ... and on a stream of its own (single-GPU runs): the critic's twenty-odd launches are independent of the actors',
-            # and every one of these persistent kernels ends with a tail in which most CUs have run out of slabs (kernel time
-            # 0.19-0.26 ms against 0.14-0.20 ms for a wave's own slab loop, tools/phase_cycles.py) -- the other chain's next
-            # kernel fills it.  HARL_CRITIC_STREAM=0 keeps one stream.
-            # Under data parallelism the second stream needs the critic's own communicator (two chains issuing into ONE
-            # communicator would have to interleave their collectives identically on every rank).
-            # Round 6, session 3: ... and only where the launches are short.  From ~150 000 rows per minibatch every heavy kernel
-            # of either chain fills the chip for 0.2 - 0.5 ms (one workgroup per CU, LDS-bound occupancy): the other chain's light
-            # kernels then wait for a whole heavy launch to drain, the sum of the kernel times is the update either way, and
-            # one stream measured as fast or faster (16.06 against 16.18 ms at 4096 threads, 8.90 / 9.00 at 2048, 5.45 / 5.58 at
-            # 1024 -- and 3.90 against 3.73 at 512 threads, where the second stream stays; profiles/r06s3_critic_stream_ab.md).
-            # HARL_CRITIC_STREAM=1 forces the second stream, 0 forbids it.
-            cs_mode = os.environ.get("HARL_CRITIC_STREAM", "auto")
-            if (dev.type == "cuda" and (not self.comm.enabled or self.critic.comm is not self.comm)
-                    and cs_mode != "0" and (cs_mode == "1" or B <= self.CRITIC_STREAM_MAX_ROWS)):
-                if getattr(self, "_critic_stream", None) is None:
-                    self._critic_stream = torch.cuda.Stream(device=dev)
-                main_s = torch.cuda.current_stream(dev)
-                self._critic_stream.wait_stream(main_s)
-                with torch.cuda.stream(self._critic_stream):
-                    cinfo = self.critic.train(self.critic_buffer, self.value_normalizer, _defer=True)
-                    critic_done = torch.cuda.Event()
-                    critic_done.record(self._critic_stream)
-            else:
+        # ---- schedule, and the critic's update where it goes first: before the host waits for the counts
+        sched = self._train_schedule(fast, B, on_gpu)
+        cs, cinfo, critic_done, stagger = None, None, None, None
+        if sched.critic == "first":
+            if sched.critic_stream:
+                cs = _stream(self, "_critic_stream")
+                cs.wait_stream(main)
+            with _on(cs):
                 cinfo = self.critic.train(self.critic_buffer, self.value_normalizer, _defer=True)
+                if cs is not None:
+                    critic_done = torch.cuda.Event()
+                    critic_done.record(cs)
+        # ---- counts, and the two facts per agent that depend on them: whether its pre-update log-probs come out of its first
+        # forward (with one full-buffer minibatch the first epoch's forward inside train() computes exactly these: same rows,
+        # same parameters), and whether it draws from the generator at all (the staggered critic's footprint)
         ev.synchronize()
         counts = self._counts_host.tolist()
-        # Round 6: the critic's update NEXT TO the actors' also where permutations are materialised (recurrent policies, several
-        # minibatches).  In the reference the critic's samplers draw from the global CPU generator AFTER every actor's, so the
-        # generator is fast-forwarded over the actors' draws first (their sizes are known: HAPPO.rng_footprint; agents without an
-        # active entry draw nothing, happo.py:119-120), the critic's train() -- on a stream of its own -- takes its permutations
-        # from exactly the state the reference's critic finds, and the generator goes back to where the actors start; at the end
-        # it is set to the state behind the critic's draws.  Every permutation and the final state are bit-identical to the
-        # in-order run.  What it buys: with GRU policies the main stream idles ~0.4 ms per agent behind the previous agent's
-        # post-update log-prob pass (a full-length chain on 6 % of the chip: 3.9 of the SMAC update's 29.5 ms, rocprofv3 trace of
-        # round 6) and then ran the critic's 2.4 ms at the very end; now the critic's launches fill those gaps.
-        rng_after = None
-        if (cinfo is None and dev.type == "cuda" and all(hasattr(a, "rng_footprint") for a in self.actor)
-                and (not self.comm.enabled or self.critic.comm is not self.comm)
-                and os.environ.get("HARL_CRITIC_STREAM", "1") != "0" and os.environ.get("HARL_CRITIC_EARLY", "1") != "0"):
-            from .buffers import consume_randperm
-            rng_sync()
-            rng_start = torch.get_rng_state()
-            for a in agent_order:
-                if counts[a] > 0.0:
-                    for n in self.actor[a].rng_footprint(self.actor_buffer[a]):
-                        consume_randperm(n)  # (the generator advance of torch.randperm(n), no permutation materialised)
-            rng_sync()
-            if getattr(self, "_critic_stream", None) is None:
-                self._critic_stream = torch.cuda.Stream(device=dev)
-            self._critic_stream.wait_stream(torch.cuda.current_stream(dev))
-            # ... one EPOCH at a time (VCritic._train_epochs), epoch k enqueued right behind agent k's update and ordered behind
-            # its event: that is where the main stream goes idle (agent k + 1's loss waits for agent k's post-update pass); run
-            # all at once up front the critic only competed with the first agent's kernels (27.7 against 28.3 ms, SMAC 3s5z).
-            # The generator keeps TWO positions: the actors' (restored after every critic epoch) and the critic's.
-            staggered = dict(gen=self.critic._train_epochs(self.critic_buffer, self.value_normalizer), state=torch.get_rng_state(),
-                             left=self.critic.critic_epoch)
-            torch.set_rng_state(rng_start)
+        fused_old = [fast[a] and self.actor[a].fuses_old_logp() and counts[a] > 0.0 for a in range(self.num_agents)]
+        if sched.critic == "staggered":
+            footprint = [n for a in agent_order if counts[a] > 0.0 for n in self.actor[a].rng_footprint(self.actor_buffer[a])]
+            cs = _stream(self, "_critic_stream")
+            cs.wait_stream(main)
+            stagger = _StaggeredCritic(self.critic._train_epochs(self.critic_buffer, self.value_normalizer),
+                                       self.critic.critic_epoch, footprint, cs)
+        # ---- the side stream
+        passes, old_all, old_ev = {}, {}, {}
 
-            def critic_epoch(after_event=None, _st=staggered):
-                if _st["left"] <= 0:
-                    return
-                rng_sync()
-                actor_state = torch.get_rng_state()
-                torch.set_rng_state(_st["state"])
-                if after_event is not None:
-                    self._critic_stream.wait_event(after_event)
-                with torch.cuda.stream(self._critic_stream):
-                    next(_st["gen"])
-                _st["left"] -= 1
-                rng_sync()
-                _st["state"] = torch.get_rng_state()
-                torch.set_rng_state(actor_state)
-            rng_after = staggered
-        # Pre-update log-probs that cannot come out of the first epoch's forward (recurrent policies: full-length unroll from
-        # rnn_states[0]; several minibatches) depend only on the agent's OWN pre-update weights, not on the agents before it
-        # (on_policy_ha_runner.py:66-83) -- so all of them are enqueued up front on a side stream, where the long, narrow
-        # recurrences (N/32 dependent chains of T steps) run next to the update kernels of the agents in front instead of in
-        # series with them; agent k's update waits for event k.
-        old_all, old_ev = {}, {}
-        side_agents = [a for a in agent_order
-                       if not (fast[a] and self.actor[a].fuses_old_logp() and counts[a] > 0.0) and os.environ.get("HARL_SIDE_STREAM", "1") != "0"]
+        def logp_inputs(a):
+            """((obs, actions, available actions, B), recurrent keywords) of agent a's log-prob passes, built once.  Its weights
+            are folded first, on the stream that is current, at every call: free when nothing has touched them since."""
+            act_a, buf_a = self.actor[a], self.actor_buffer[a]
+            act_a.actor.fold()
+            if a not in passes:
+                kw_a = dict(rnn_states=buf_a.rnn_states[0], masks=buf_a.flat("masks")) if act_a.actor.recurrent else {}
+                avail = None if buf_a.available_actions is None else buf_a.flat("available_actions")
+                passes[a] = ((buf_a.flat("obs"), buf_a.flat("actions"), avail, B), kw_a)
+            return passes[a]
+
         def enqueue_old_logp(a):
             """Agent a's pre-update pass on the side stream (+ the event its update waits for)."""
-            act_a, buf_a = self.actor[a], self.actor_buffer[a]
             with torch.cuda.stream(self._side_stream):
-                act_a.actor.fold()
-                kw_a = dict(rnn_states=buf_a.rnn_states[0], masks=buf_a.flat("masks")) if act_a.actor.recurrent else {}
-                act_a._logp_pass(buf_a.flat("obs"), buf_a.flat("actions"),
-                                 None if buf_a.available_actions is None else buf_a.flat("available_actions"), B, old_all[a], **kw_a)
+                args_a, kw_a = logp_inputs(a)
+                self.actor[a]._logp_pass(*args_a, old_all[a], **kw_a)
                 old_ev[a] = torch.cuda.Event()
                 old_ev[a].record(self._side_stream)
 
-        # ... ONE AGENT AHEAD of the main stream (round 6, second session): enqueueing all of them up front is ~0.3 ms of host time
-        # each -- the raw rocprofv3 trace of the 8-agent recurrent update showed the main queue EMPTY for the first 2.6 of its 22.7
-        # ms while the host was still feeding the side stream.  The first agent's pass goes out here, agent k + 1's right behind
-        # the launches of agent k's update (2.5 ms of queued GPU work for a 0.47 ms pass): same kernels, same operands per agent.
-        # HARL_SIDE_AHEAD=0: all up front, as before.
-        side_lazy = os.environ.get("HARL_SIDE_AHEAD", "1") != "0"
-        side_pending = []
-        if side_agents:
-            if getattr(self, "_side_stream", None) is None:
-                self._side_stream = torch.cuda.Stream(device=dev)
-            main = torch.cuda.current_stream(dev)
-            self._side_stream.wait_stream(main)
-            for a in side_agents:
-                act_a, buf_a = self.actor[a], self.actor_buffer[a]
-                old_all[a] = torch.empty(B, act_a.actor.act_w, dtype=torch.float32, device=dev)
-            side_pending = list(side_agents)
-            for a in (side_pending[:1] if side_lazy else list(side_pending)):
-                enqueue_old_logp(a)
-                side_pending.remove(a)
-        pending = []
-        # Post-update log-probs of RECURRENT policies (full-length unroll: N/32 dependent chains of T steps, ~0.5 ms on 32 waves
-        # of the chip at the SMAC sizes) go to a stream of their own: the next agent's first forward -- sequence tables, input
-        # image, MLP layers, the training GRU forward -- needs nothing from them; only its first LOSS launch consumes the factor
-        # and waits for the event (HAPPO._await_factor).  Same kernels, same operands, same order per tensor: bit-identical
-        # results.  HARL_POST_STREAM=0 keeps the pass on the main stream.
-        post_ok = dev.type == "cuda" and os.environ.get("HARL_POST_STREAM", "1") != "0"
-        factor_ev, keep_alive, prev_overlapped = None, [], False
-        # (device "cpu" exists under the tests' launch recorder only, which pins the reference's one pass per agent)
-        last_post = os.environ.get("HARL_LAST_POST_PASS", "0") == "1" or dev.type != "cuda"
+        side_pending = [a for a in agent_order if not fused_old[a]] if sched.side else []
+        if side_pending:
+            _stream(self, "_side_stream").wait_stream(main)
+            for a in side_pending:
+                old_all[a] = torch.empty(B, self.actor[a].actor.act_w, dtype=torch.float32, device=dev)
+            for _ in range(1 if sched.side_ahead else len(side_pending)):
+                enqueue_old_logp(side_pending.pop(0))
+        # ---- the agents, in order
+        pending, keep_alive = [], []
+        factor_ev, prev_overlapped = None, False
         for pos, agent_id in enumerate(agent_order):
             buf, actor = self.actor_buffer[agent_id], self.actor[agent_id]
             if agent_id in old_ev:  # this agent's networks / workspaces are in use on the side stream until then
-                torch.cuda.current_stream(dev).wait_event(old_ev[agent_id])
+                main.wait_event(old_ev[agent_id])
             buf.update_factor(factor)
             if prev_overlapped:  # the post stream still reads the previous agent's pre-update log-probs: do not write into them
                 keep_alive.append(self._logp_old)
                 self._logp_old = None
-            obs, actions = buf.flat("obs"), buf.flat("actions")
-            avail = None if buf.available_actions is None else buf.flat("available_actions")
             if self._logp_old is None or self._logp_old.shape != (B, actor.actor.act_w):
                 self._logp_old = torch.empty(B, actor.actor.act_w, dtype=torch.float32, device=dev)
-            actor.actor.fold()
-            rnn_kw = dict(rnn_states=buf.rnn_states[0], masks=buf.flat("masks")) if actor.actor.recurrent else {}
+            logp_args, rnn_kw = logp_inputs(agent_id)
             adv_a = advantages if self.state_type == "EP" else advantages[:, :, agent_id].contiguous()
             kw = dict(_pre=(mom_all[agent_id], counts[agent_id]), _defer=True) if fast[agent_id] else {}
-            # pre-update log-probs (:66-83).  With one full-buffer minibatch the first epoch's forward inside train()
-            # computes exactly these (same rows, same parameters), so they are taken from there.
-            fused_old = fast[agent_id] and actor.fuses_old_logp() and counts[agent_id] > 0.0
-            if fused_old:
+            if fused_old[agent_id]:  # pre-update log-probs (:66-83): out of the first forward, off the side stream, or here
                 kw["_old_logp_out"] = self._logp_old
             elif agent_id in old_all:
                 self._logp_old = old_all.pop(agent_id)
             else:
-                actor._logp_pass(obs, actions, avail, B, self._logp_old, **rnn_kw)
+                actor._logp_pass(*logp_args, self._logp_old, **rnn_kw)
             if factor_ev is not None and hasattr(actor, "_factor_ready"):
                 actor._factor_ready = factor_ev
             info = actor.train(buf, adv_a, self.state_type, **kw)               # :86-93
-            if side_pending:  # the next agent's pre-update pass, behind this agent's queued launches (see enqueue_old_logp)
+            if side_pending:  # the next agent's pre-update pass, behind this agent's queued launches (``side_ahead``)
                 enqueue_old_logp(side_pending.pop(0))
-            if rng_after is not None and rng_after["left"] > 0:  # one critic epoch behind this agent's optimiser steps
+            if stagger is not None and stagger.left > 0:  # one critic epoch behind this agent's optimiser steps
                 ev_a = torch.cuda.Event()
-                ev_a.record(torch.cuda.current_stream(dev))
-                critic_epoch(ev_a)
+                ev_a.record(main)
+                stagger.epoch(ev_a)
             if factor_ev is not None:  # (an update that never reached a loss launch has not waited yet)
                 if hasattr(actor, "_factor_ready"):
                     actor._factor_ready = None
-                torch.cuda.current_stream(dev).wait_event(factor_ev)
+                main.wait_event(factor_ev)
                 factor_ev = None
             pending.append((len(actor_train_infos), info, actor._INFO_KEYS) if torch.is_tensor(info) else None)
             actor_train_infos.append(info)
             nxt = agent_order[pos + 1] if pos + 1 < len(agent_order) else None
-            prev_overlapped = bool(post_ok and nxt is not None and actor.actor.recurrent and hasattr(self.actor[nxt], "_factor_ready"))
-            if nxt is None and not last_post:
-                # the factor behind the LAST agent of the order is handed to nobody (on_policy_ha_runner.py:96-124 computes it
-                # and drops it): no clone, no forward over the whole batch.  HARL_LAST_POST_PASS=1 runs it all the same.
+            prev_overlapped = bool(sched.post_stream and nxt is not None and actor.actor.recurrent
+                                   and hasattr(self.actor[nxt], "_factor_ready"))
+            if nxt is None and not sched.last_post:
                 continue
-            if prev_overlapped:
-                if getattr(self, "_post_stream", None) is None:
-                    self._post_stream = torch.cuda.Stream(device=dev)
-                ps = self._post_stream
-                ps.wait_stream(torch.cuda.current_stream(dev))  # this agent's optimiser steps are complete
+            ps = _stream(self, "_post_stream") if prev_overlapped else None
+            if ps is not None:
+                ps.wait_stream(main)  # this agent's optimiser steps are complete
                 keep_alive += [factor, self._logp_old]
-                with torch.cuda.stream(ps):
-                    new_factor = factor.clone()
-                    actor._logp_pass(obs, actions, avail, B, None, old_logp=self._logp_old, factor=new_factor.reshape(B), **rnn_kw)
+            with _on(ps):
+                new_factor = factor.clone()
+                # post-update log-probs fused with factor *= agg(exp(new - old))   (:96-124)
+                actor._logp_pass(*logp_args, None, old_logp=self._logp_old, factor=new_factor.reshape(B), **rnn_kw)
+                if ps is not None:
                     factor_ev = torch.cuda.Event()
                     factor_ev.record(ps)
-                factor = new_factor
-                continue
-            new_factor = factor.clone()
-            # post-update log-probs fused with factor *= agg(exp(new - old))   (:96-124)
-            actor._logp_pass(obs, actions, avail, B, None, old_logp=self._logp_old, factor=new_factor.reshape(B), **rnn_kw)
             factor = new_factor
+        # ---- close
         if keep_alive:  # tensors of the main stream's allocator pool that the post stream has read
-            torch.cuda.current_stream(dev).wait_stream(self._post_stream)
+            main.wait_stream(self._post_stream)
             keep_alive.clear()
-        if rng_after is not None:  # epochs not handed out yet (fewer agents than critic epochs), then the critic's statistics
-            while rng_after["left"] > 0:
-                critic_epoch(None)
-            for _ in rng_after["gen"]:  # (run the generator to its end)
-                pass
-            with torch.cuda.stream(self._critic_stream):
+        if stagger is not None:  # epochs not handed out yet (fewer agents than critic epochs), then the critic's statistics
+            stagger.finish()
+            with torch.cuda.stream(cs):
                 cinfo = self.critic._train_result(True)
                 critic_done = torch.cuda.Event()
-                critic_done.record(self._critic_stream)
+                critic_done.record(cs)
         if cinfo is None:
             cinfo = self.critic.train(self.critic_buffer, self.value_normalizer, _defer=True)
         if critic_done is not None:
-            torch.cuda.current_stream(dev).wait_event(critic_done)
+            main.wait_event(critic_done)
         rng_sync()  # the global CPU generator is exactly where the reference leaves it
-        if rng_after is not None:  # ... i.e. behind the critic's draws, which were taken from their own position (see above)
-            torch.set_rng_state(rng_after["state"])
+        if stagger is not None:  # ... i.e. behind the critic's draws, which were taken from their own position
+            torch.set_rng_state(stagger.state)
         dev_infos = [p[1] for p in pending if p is not None] + [cinfo]
         flat = torch.cat([t.reshape(-1) for t in dev_infos]).cpu().tolist()  # the single end-of-train read-back
         self._check_comms()
@@ -419,8 +486,7 @@ class OnPolicyHARunner:
             if hasattr(a, "fuses_old_logp") and a.fuses_old_logp():
                 items.append((a.actor, buf.flat("obs")))
         c = self.critic
-        crit = (c.critic_num_mini_batch == 1 and not (c.use_recurrent_policy or c.use_naive_recurrent_policy)
-                and hasattr(c, "_inputs_prepared"))
+        crit = hasattr(c, "_inputs_prepared") and c.one_full_minibatch()
         if crit:
             c.critic.invalidate_caches()
             items.append((c.critic, self.critic_buffer.flat("share_obs")))
@@ -434,18 +500,6 @@ class OnPolicyHARunner:
         """Sum of the actors' and the critic's ``graph_stats()`` (HARL_GRAPH=1: captured / replayed / eager optimiser steps)."""
         from .graphs import sum_stats
         return sum_stats(list(self.actor) + [self.critic])
-
-    def _critic_first_ok(self, fast) -> bool:
-        """May the critic update be enqueued before the actors'?  Only when nothing in train() materialises a permutation
-        (one full-buffer minibatch everywhere, feed-forward nets, HAPPO-family actors): then every sampler merely advances
-        the CPU generator by a count, the final generator state does not depend on the order of those advances, and the
-        critic reads nothing the actors write."""
-        if not all(fast) or os.environ.get("HARL_CRITIC_FIRST", "1") == "0":
-            return False
-        c = self.critic
-        if c.critic_num_mini_batch != 1 or c.use_recurrent_policy or c.use_naive_recurrent_policy:
-            return False
-        return all(hasattr(a, "fuses_old_logp") and a.fuses_old_logp() for a in self.actor)
 
     def after_update(self):
         for b in self.actor_buffer:

@@ -190,6 +190,11 @@ class VCritic:
         d = self._info - before
         return d[0], d[1]
 
+    def one_full_minibatch(self) -> bool:
+        """True when every optimiser step of train() sees every buffer row, in order (HAPPO.fuses_old_logp's fact, for the
+        critic): no permutation is materialised, and the update's input image can be built up front."""
+        return self.critic_num_mini_batch == 1 and not (self.use_recurrent_policy or self.use_naive_recurrent_policy)
+
     def train(self, critic_buffer: OnPolicyCriticBufferEP, value_normalizer: Optional[ValueNorm] = None, _defer=False):
         """critic_epoch x critic_num_mini_batch updates (v_critic.py:159-200).  ``_defer`` (runner-internal): return the
         averaged statistics as a device tensor and leave deferred RNG advances pending."""

@@ -293,21 +293,25 @@ def digest(trace):
     return hashlib.sha256(json.dumps(trace, separators=(",", ":")).encode()).hexdigest()
 
 
-def summarise(traces, keep=()):
+def call_name(c):
+    """The name a recorded call goes by in the fixture's table: "entry:tag"."""
+    return f"{c[0]}:{c[1] or ''}"
+
+
+def summarise(traces, keep=(), name=call_name):
     """What the committed fixture keeps of the full traces (they are several hundred KB): per configuration every call's entry
     point and tag in order -- as indices into ONE table of "entry:tag" names -- and a SHA-256 of the full trace.  ``keep``: the
     name table of the fixture that is being extended; its names keep their indices (and the recorded lines their bytes), new
-    names follow."""
-    names = list(keep) + sorted({f"{c[0]}:{c[1] or ''}" for t in traces.values() for c in t} - set(keep))
+    names follow.  ``name``: what one entry of a trace is called in that table (tools/stream_trace.py has entries of its own)."""
+    names = list(keep) + sorted({name(c) for t in traces.values() for c in t} - set(keep))
     at = {n: i for i, n in enumerate(names)}
-    return dict(names=names, traces={k: dict(calls=[at[f"{c[0]}:{c[1] or ''}"] for c in t], sha256=digest(t))
-                                     for k, t in traces.items()})
+    return dict(names=names, traces={k: dict(calls=[at[name(c)] for c in t], sha256=digest(t)) for k, t in traces.items()})
 
 
-def compare(want, got):
+def compare(want, got, name=call_name):
     """Full traces ``got`` against the fixture ``want`` (summarise), as lines of text (empty: equal): per configuration the
     first call whose entry point or tag differs, or that only the arguments do (then: first_difference of two --full dumps)."""
-    out, have = [], summarise(got)
+    out, have = [], summarise(got, name=name)
     for k in sorted(set(want["traces"]) | set(have["traces"])):
         a, b = want["traces"].get(k), have["traces"].get(k)
         if a is None or b is None:
@@ -343,6 +347,13 @@ def normalise(traces):
     return json.loads(json.dumps(traces))
 
 
+def write_fixture(path, fx):
+    """A summarise() result as the committed file: the name table, then one configuration per line."""
+    with open(path, "w") as f:
+        f.write('{"names": ' + json.dumps(fx["names"]) + ',\n "traces": {\n' + ",\n".join(
+            f'  {json.dumps(k)}: {json.dumps(t, separators=(",", ":"))}' for k, t in fx["traces"].items()) + "\n}}\n")
+
+
 def all_traces():
     import pytest
     from tests.test_multidiscrete_cpu import stub_kernels
@@ -375,9 +386,7 @@ def main():
                 with open(a.write) as f:
                     keep = json.load(f)["names"]
             fx = summarise(traces, keep)
-            with open(a.write, "w") as f:  # one configuration per line
-                f.write('{"names": ' + json.dumps(fx["names"]) + ',\n "traces": {\n' + ",\n".join(
-                    f'  {json.dumps(k)}: {json.dumps(t, separators=(",", ":"))}' for k, t in fx["traces"].items()) + "\n}}\n")
+            write_fixture(a.write, fx)
         else:
             with open(a.check) as f:
                 lines = compare(json.load(f), traces)
