@@ -1849,6 +1849,14 @@ def check_bench_config_parity(logp: str = "recipe", n_threads: int = 4096, n_per
         out[f"_{key}_rel"] = err
         out[f"_{key}_oracle_own_uncertainty"] = floor
         out[f"{key}_excess"] = err / max(1e-5, FULL_SIZE_NOISE * floor)
+        # the figure the tests hold to 1e-5 FLAT, entry by entry: the distance from the fp32 oracle -- except on an entry where
+        # the fp32 oracle's own figure is 1e-5 or more from its float64 twin (from identical inputs: it is no 1e-5 yardstick
+        # there), which is held to the same 1e-5 against the float64 twin instead.  Which entries those are depends on the
+        # host's fp32 arithmetic (BLAS kernels of its CPU): one ReLU decision on a heavy sample that the fp32 oracle takes
+        # differently from exact arithmetic moves a gradient by 1e-5 of its norm.
+        own = rel(get(o), get(o64))
+        out[f"_{key}_flat_rel"] = float(np.where(own < 1e-5, rel(get(hip), get(o)), rel(get(hip), get(o64))).max())
+        out[f"_{key}_entries_held_to_float64"] = float((own >= 1e-5).sum())
 
     names = ("policy_loss", "dist_entropy", "grad_norm", "ratio")
     for c, nm in enumerate(names):
@@ -1878,7 +1886,10 @@ def check_bench_config_parity(logp: str = "recipe", n_threads: int = 4096, n_per
         else:
             out[f"critic_update_{nm}_rel"] = float(rel(hip["ctr"][:, c], o["ctr"][:, c]).max())
     keys = ("policy_loss", "dist_entropy", "actor_grad_norm", "ratio")
-    pooled(lambda run: np.array([[float(i[k]) for k in keys] for i in run["infos"]], dtype=np.float64), "actor_infos")
+    infos = lambda run: np.array([[float(i[k]) for k in keys] for i in run["infos"]], dtype=np.float64)  # noqa: E731  [agent, key]
+    pooled(infos, "actor_infos")
+    for c, k in enumerate(keys):  # (each averaged statistic on its own: an average is as well conditioned as its terms)
+        out[f"_actor_infos_{k}_rel"] = float(rel(infos(hip)[:, c], infos(o)[:, c]).max())
     out["critic_info_rel"] = rel_err([hip["cinfo"]["value_loss"], hip["cinfo"]["critic_grad_norm"]],
                                      [o["cinfo"]["value_loss"], o["cinfo"]["critic_grad_norm"]])
     ovn = o["vn"]
