@@ -1,0 +1,259 @@
+// rect.hip -- layers with a 256-wide side and a narrower one (harl/models/base/mlp.py:7-70 with hidden_sizes such as
+// [256, 128], [128, 256] or [256, 128, 64]), gfx950.  Opt-in route HARL_MIXED_256=1 (harl_amd/configs.py).
+//
+// panel.hip walks K in panels because three bf16 images of a 256-row matrix do not fit the LDS; its k_panel is built around
+// eight accumulator tiles (128 registers) and a 32-column panel.  A layer 256 -> 64 / 128 has 2 / 4 output row tiles, and its
+// backward (rows = 256 input features) reduces over 64 / 128 columns only.  k_panel_rect<MT, MODE> is the K-panel walk for
+// MT = 2 / 4 / 8 row tiles with the geometry chosen per MT:
+//
+//   unit      A SUB-PANEL is 32 columns (2 k-steps of v_mfma_f32_32x32x16_bf16) of all 32 MT rows: 3 terms x MT x 2 fragments
+//             x 1 KiB.  It is what split_gemm<MT, 2> multiplies and what a short last panel is counted in.
+//   panel     8 / MT sub-panels = 48 KiB of images whatever MT is: 128 columns at MT = 2, 64 at MT = 4, 32 at MT = 8.  A
+//             256-column reduction is 2 / 4 / 8 panels, i.e. a quarter / half the barriers of k_panel at MT = 2 / 4.  KP = 96 at
+//             MT = 4 is one full panel and one of a single sub-panel.
+//   slabs     one slab (32 rows) per wave, four per workgroup iteration as in k_panel: the matrix streams from L2 once per 128
+//             rows and the tail logic (dead waves of the last iteration stage and meet every barrier, write nothing) is the same.
+//   prefetch  a panel is 1024 fragments per term = 4 per thread = 32 fp32 weights.  They are loaded into registers for panel
+//             p + 1 BEFORE panel p is multiplied and split into LDS after it, so the L2 latency of the weights lies under the
+//             MFMAs instead of in front of them (k_panel loads, splits and writes between two barriers).  The slab's own x
+//             columns of panel p are loaded in front of that prefetch: vector loads return in order, and the first MFMA must
+//             not wait for the weights of the NEXT panel.
+//   MT 2 / 4  32 / 64 accumulator registers: the kernel fits 256 registers, __launch_bounds__(256, 2), ONE 48 KiB buffer and
+//             two workgroups per CU (96 of 160 KiB).  The second wave of a SIMD multiplies while the first splits weights or
+//             runs its LayerNorm epilogue -- overlap a second buffer in the same workgroup cannot give, because a wave's own
+//             split and its own MFMAs are one instruction stream.  Two barriers per panel (filled / drained).
+//   MT 8      128 accumulator registers + the LayerNorm backward's x_hat and output (3 x 128 live at its peak): one wave per
+//             SIMD, as k_panel.  Nothing shares the SIMD, and 160 KiB belong to one workgroup: TWO 48 KiB buffers, panel p + 1
+//             is written while others still read panel p, one barrier per panel (8 per slab where k_panel has 16).
+//   forward  : x_hat_out = norm(relu(W' x_in + b'))            x_in = ATL(KP) image, KP a multiple of 32 up to 512
+//   backward : dz_in = relu' . LNbwd(W'^T dz_out)               (HI, HO) over {64, 128, 256}^2
+// The GEMM is split_mfma.h's exact three-term bf16 split, six products, fp32 accumulation; x_hat / ReLU mask words / rstd
+// leave in the layouts of the 64 / 128-wide layer kernels (fwd_epilogue.h) and of k_panel, so the head kernels,
+// harl_mlp_dw_partials and harl_mlp_bwd_dx read them unchanged.  Rows past M inside the last slab are computed like any
+// other: they never enter a sum because dz is 0 there (the loss kernels write it so, and LNbwd of a zero row is a zero row).
+#include "common.h"
+#include "split_mfma.h"
+#include "../../include/harl_hip.h"
+
+using namespace harl;
+
+namespace {
+int bad(const char *m) {
+  set_error(m);
+  return -2;
+}
+
+constexpr int PANEL_FRAGS = 1024;                    // u32x4 fragments per term and panel (16 KiB): 8 / MT sub-panels
+constexpr int PER_THREAD = PANEL_FRAGS / WG_THREADS;  // 4 fragments = 32 fp32 weights per thread and panel
+
+// the fp32 weights of panel p (sub-panels NSUB p .. NSUB p + nsub - 1) that this thread splits, into registers.
+//   TRANSPOSED = false: A[row][k] = Wp[row * ldw + k]  (k < kvalid, else 0)       forward, Wp = [32 MT][ldw]
+//   TRANSPOSED = true : A[row][k] = Wp[k * ldw + row]                              backward dX, Wp = [K][32 MT]
+// Fragment e of a panel: sub-panel e / (128 MT), then [tile][k-step j][lane] as split_gemm<MT, 2> reads it.
+// Addresses: fragment u of a thread differs from its fragment 0 by a whole sub-panel or by whole row tiles, and register c of
+// a fragment by the constant feat_base(c), so every load is (scalar base of (u, c)) + ONE lane offset per thread -- 32 lane
+// addresses would otherwise stay live across the panel loop, next to the accumulators of two waves per SIMD.
+template <int MT, bool TRANSPOSED>
+__device__ __forceinline__ void load_panel(float (&w)[PER_THREAD][8], const float *__restrict__ Wp, int ldw, int kvalid, int p,
+                                           int nsub) {
+  constexpr int SUB = MT * 128, NSUB = 8 / MT;
+  const int r0 = threadIdx.x % SUB, ln = r0 & 63, j = (r0 >> 6) & 1, m0 = 32 * (r0 >> 7) + (ln & 31), kl = 16 * j + 4 * (ln >> 5);
+  const unsigned voff = TRANSPOSED ? (unsigned)(kl * ldw + m0) : (unsigned)(m0 * ldw + kl);
+#pragma unroll
+  for (int u = 0; u < PER_THREAD; ++u) {
+    const int sub = (u * WG_THREADS) / SUB;          // (compile time per u: 256 threads never straddle a sub-panel)
+    const int dm = 32 * (((u * WG_THREADS) % SUB) >> 7);  // ... and this fragment's rows are dm below those of fragment 0
+    const int ks = 32 * (p * NSUB + sub);
+    if (sub < nsub) {  // (workgroup-uniform)
+#pragma unroll
+      for (int c = 0; c < 8; ++c) {
+        const int kc = ks + feat_base(c);  // k = kc + kl
+        const float *base = TRANSPOSED ? Wp + (kc * ldw + dm) : Wp + (dm * ldw + kc);
+        const bool in = kc + kl < kvalid;
+        const float v = base[in ? voff : 0u];
+        w[u][c] = in ? v : 0.f;
+      }
+    } else {
+#pragma unroll
+      for (int c = 0; c < 8; ++c) w[u][c] = 0.f;
+    }
+  }
+}
+
+// ... split (round to nearest) and written as the three images of the panel: buf[sub][term][tile][j][lane]
+template <int MT>
+__device__ __forceinline__ void commit_panel(u32x4 *__restrict__ buf, const float (&w)[PER_THREAD][8], int nsub) {
+  constexpr int SUB = MT * 128;
+#pragma unroll
+  for (int u = 0; u < PER_THREAD; ++u) {
+    const int sub = (u * WG_THREADS) / SUB;
+    if (sub >= nsub) continue;  // (workgroup-uniform)
+    const int r = (threadIdx.x + u * WG_THREADS) % SUB;
+    unsigned q[3][4];
+#pragma unroll
+    for (int c = 0; c < 4; ++c) split3_rne(w[u][2 * c], w[u][2 * c + 1], q[0][c], q[1][c], q[2][c]);
+#pragma unroll
+    for (int term = 0; term < 3; ++term) buf[(sub * 3 + term) * SUB + r] = u32x4{q[term][0], q[term][1], q[term][2], q[term][3]};
+  }
+}
+
+// the slab's 32 columns of sub-panel s: pieces 4 s .. 4 s + 3 of its ATL(KP) image (xp = the slab's image + lane)
+__device__ __forceinline__ void load_cols(const f32x4 *__restrict__ xp, int s, float (&x)[16]) {
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const f32x4 v = xp[(4 * s + q) * WAVE];
+    x[4 * q + 0] = v[0];
+    x[4 * q + 1] = v[1];
+    x[4 * q + 2] = v[2];
+    x[4 * q + 3] = v[3];
+  }
+}
+
+// A kernel argument as the loop body sees it anew in every workgroup iteration.  What depends on it (the bias values, the lane
+// addresses of the epilogue's loads and stores) is then formed where it is used instead of once in front of the loop, where it
+// would hold registers for the kernel's lifetime -- the difference between 256 registers and a spill at two waves per SIMD.
+template <typename T>
+__device__ __forceinline__ T *per_iteration(T *p) {
+  asm volatile("" : "+s"(p));
+  return p;
+}
+
+// MODE 0 forward, 1 backward
+template <int MT, int MODE>
+__global__ __launch_bounds__(WG_THREADS, MT == 8 ? 1 : 2) void k_panel_rect(
+    const float *__restrict__ xin, int KP, const float *__restrict__ Wp, int ldw, int kvalid, const float *__restrict__ bp,
+    float *__restrict__ xout, uint32_t *__restrict__ mask_out, float *__restrict__ rstd_out, const float *__restrict__ xprev,
+    const uint32_t *__restrict__ mask_prev, const float *__restrict__ rstd_prev, long n_slabs) {
+  constexpr bool BWD = MODE == 1;
+  constexpr int H = 32 * MT, NSUB = 8 / MT, NBUF = MT == 8 ? 2 : 1, SUB = MT * 128, BUF = 3 * PANEL_FRAGS;
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  u32x4 *img = reinterpret_cast<u32x4 *>(lds);
+  const int lane = threadIdx.x & 63, wave = wave_id(), i = lane & 31, h = lane >> 5;
+  const int n_sub = KP / 32, n_panels = (n_sub + NSUB - 1) / NSUB;
+  const long n_iter = (n_slabs + WAVES_PER_WG - 1) / WAVES_PER_WG;
+  for (long it = blockIdx.x; it < n_iter; it += gridDim.x) {  // uniform trip count: barriers inside
+    const long s_raw = it * WAVES_PER_WG + wave;
+    const bool live = s_raw < n_slabs;
+    const long slab = live ? s_raw : n_slabs - 1;
+    const f32x4 *xp = reinterpret_cast<const f32x4 *>(xin + slab * (long)KP * SLAB) + lane;
+    f32x16 acc[MT];
+    // (the bias is read again every iteration: hoisted out of this loop it would hold 16 MT registers for the kernel's lifetime)
+    const float *bpi = per_iteration(bp);
+#pragma unroll
+    for (int t = 0; t < MT; ++t)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[t][r] = BWD ? 0.f : bpi[32 * t + (r & 3) + 8 * (r >> 2) + 4 * h];
+    float w[PER_THREAD][8];
+    int nsub_p = n_sub < NSUB ? n_sub : NSUB;
+    load_panel<MT, BWD>(w, Wp, ldw, kvalid, 0, nsub_p);
+    __syncthreads();  // the last panel of the iteration before is no longer being read
+    commit_panel<MT>(img, w, nsub_p);
+    for (int p = 0; p < n_panels; ++p) {
+      // this slab's columns of the panel's first sub-panel, then the prefetch; the columns of sub-panel s + 1 are asked for
+      // while sub-panel s multiplies (by then the prefetch in front of them has long returned)
+      float xa[16];
+      load_cols(xp, p * NSUB, xa);
+      const bool more = p + 1 < n_panels;
+      const int rest = n_sub - (p + 1) * NSUB, nsub_next = rest < NSUB ? rest : NSUB;
+      if (more) load_panel<MT, BWD>(w, Wp, ldw, kvalid, p + 1, nsub_next);
+      __syncthreads();  // panel p is complete (and, with two buffers, panel p - 1 is no longer being read)
+      const u32x4 *wl = img + (p % NBUF) * BUF + lane;
+#pragma unroll
+      for (int sub = 0; sub < NSUB; ++sub)
+        if (sub < nsub_p) {
+          u32x4 x1[2], x2[2], x3[2];
+          split_acts<16>(xa, x1, x2, x3);
+          float xb[16];
+          if (sub + 1 < nsub_p) load_cols(xp, p * NSUB + sub + 1, xb);
+          split_gemm<MT, 2>(wl + sub * 3 * SUB, x1, x2, x3, acc, [](int) {});
+          if (sub + 1 < nsub_p) {
+#pragma unroll
+            for (int c = 0; c < 16; ++c) xa[c] = xb[c];
+          }
+        }
+      if (more) {
+        if (NBUF == 1) __syncthreads();  // one buffer: every wave has drained panel p
+        commit_panel<MT>(img + ((p + 1) % NBUF) * BUF, w, nsub_next);
+      }
+      nsub_p = nsub_next;
+    }
+    if (!live) continue;
+    constexpr int NR = H / 2, NW = (NR + 31) / 32;
+    float *xo = per_iteration(xout);
+    if constexpr (!BWD) {
+      uint32_t *mo = per_iteration(mask_out);
+      float *ro = per_iteration(rstd_out);
+      uint32_t bits[NW];
+#pragma unroll
+      for (int wd = 0; wd < NW; ++wd) bits[wd] = 0u;
+      float v[NR];
+      float sum = 0.f;
+#pragma unroll
+      for (int R = 0; R < NR; ++R) {
+        v[R] = relu_push(acc[R >> 4][R & 15], bits[R >> 5]);
+        sum += v[R];
+      }
+      sum = wave_sum32(sum);
+      const float mean = sum * (1.0f / H);
+      float vs = 0.f;
+#pragma unroll
+      for (int R = 0; R < NR; ++R) {
+        v[R] -= mean;
+        vs += v[R] * v[R];
+      }
+      vs = wave_sum32(vs);
+      const float rstd = 1.0f / sqrtf(vs * (1.0f / H) + 1e-5f);
+#pragma unroll
+      for (int R = 0; R < NR; ++R) v[R] *= rstd;
+      atl_store<H>(xo, slab, lane, v);
+#pragma unroll
+      for (int wd = 0; wd < NW; ++wd) mo[(slab * NW + wd) * WAVE + lane] = bits[wd];
+      if (lane < 32) ro[slab * SLAB + lane] = rstd;
+    } else {
+      float dx[NR], xh[NR], out[NR];
+#pragma unroll
+      for (int R = 0; R < NR; ++R) dx[R] = acc[R >> 4][R & 15];
+      atl_load<H>(per_iteration(xprev), slab, lane, xh);
+      ln_bwd_relu_regs<H>(dx, xh, per_iteration(mask_prev), per_iteration(rstd_prev)[slab * SLAB + i], lane, slab, out);
+      atl_store<H>(xo, slab, lane, out);
+    }
+  }
+}
+
+template <int MT, int MODE>
+void launch_rect(const float *xin, int KP, const float *Wp, int ldw, int kvalid, const float *bp, float *xout,
+                 uint32_t *mask_out, float *rstd_out, const float *xprev, const uint32_t *mask_prev, const float *rstd_prev,
+                 long n_slabs, hipStream_t s) {
+  constexpr int NBUF = MT == 8 ? 2 : 1, WG_PER_CU = MT == 8 ? 1 : 2;
+  const size_t shm = (size_t)NBUF * 3 * PANEL_FRAGS * sizeof(u32x4);
+  allow_big_lds(k_panel_rect<MT, MODE>, shm);
+  hipLaunchKernelGGL((k_panel_rect<MT, MODE>), dim3(persistent_grid(n_slabs, WG_PER_CU)), dim3(WG_THREADS), shm, s, xin, KP, Wp,
+                     ldw, kvalid, bp, xout, mask_out, rstd_out, xprev, mask_prev, rstd_prev, n_slabs);
+}
+
+bool width_ok(int h) { return h == 64 || h == 128 || h == 256; }
+}  // namespace
+
+extern "C" int harl_mlp_rect_fwd(const float *xin, long M, int KP, const float *Wp, int D, const float *bp, int HO, float *xout,
+                                 uint32_t *relu_mask, float *rstd, void *stream) {
+  if (M <= 0) return 0;
+  if (!width_ok(HO)) return bad("harl_mlp_rect_fwd: output width must be 64, 128 or 256");
+  if (D < 1 || KP % 32 != 0 || KP < D || KP > 512) return bad("harl_mlp_rect_fwd: KP must be a multiple of 32, >= D >= 1 and <= 512");
+  const long n_slabs = n_slabs_of(M);
+#define RECT(MTv) launch_rect<MTv, 0>(xin, KP, Wp, D, D, bp, xout, relu_mask, rstd, nullptr, nullptr, nullptr, n_slabs, (hipStream_t)stream)
+  if (HO == 64) RECT(2); else if (HO == 128) RECT(4); else RECT(8);
+#undef RECT
+  return check_launch("harl_mlp_rect_fwd");
+}
+
+extern "C" int harl_mlp_rect_bwd(const float *dz, const float *xprev, const uint32_t *relu_mask_prev, const float *rstd_prev,
+                                 long M, int HO, int HI, const float *Wp, float *dz_prev, void *stream) {
+  if (M <= 0) return 0;
+  if (!width_ok(HO) || !width_ok(HI)) return bad("harl_mlp_rect_bwd: both widths must be 64, 128 or 256");
+  const long n_slabs = n_slabs_of(M);
+  // dx_hat[i] = sum_o Wp[o][i] dz[o]: rows = input features, k = output features, Wp = [HO][HI] (row stride HI)
+#define RECT(MTv) launch_rect<MTv, 1>(dz, HO, Wp, HI, HO, nullptr, dz_prev, nullptr, nullptr, xprev, relu_mask_prev, rstd_prev, n_slabs, (hipStream_t)stream)
+  if (HI == 64) RECT(2); else if (HI == 128) RECT(4); else RECT(8);
+#undef RECT
+  return check_launch("harl_mlp_rect_bwd");
+}

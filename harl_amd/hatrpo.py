@@ -18,7 +18,8 @@ import torch
 from . import _lib
 from ._lib import call, ptr, stream
 from .buffers import OnPolicyActorBuffer, consume_randperm, rng_sync
-from .configs import CAT_WIDE_REFUSALS, GAUSS_WIDE_REFUSALS, gauss_wide_enabled, trpo_cat_wide_enabled
+from .configs import (CAT_WIDE_REFUSALS, GAUSS_WIDE_REFUSALS, MIXED_256_REFUSALS, gauss_wide_enabled, is_mixed_256,
+                      mixed_256_enabled, trpo_cat_wide_enabled)
 from .happo import OnPolicyBase
 from .nets import build_seq, consume_policy_init_rng, seq_compact
 from .valuenorm import _as_dev
@@ -33,6 +34,8 @@ class HATRPO(OnPolicyBase):
         if act_space.__class__.__name__ == "Box" and int(act_space.shape[0]) > 32 and gauss_wide_enabled():
             # (harl_actor_head_fvp, harl_trpo_begin and the line search read the log_std block from the scalar row)
             raise NotImplementedError(GAUSS_WIDE_REFUSALS["hatrpo" if int(act_space.shape[0]) <= 64 else "n"])
+        if is_mixed_256(list(args["hidden_sizes"])) and mixed_256_enabled():  # (the tangent pass: harl_mlp_panel_tangent)
+            raise NotImplementedError(MIXED_256_REFUSALS["hatrpo"])
         super().__init__(args, obs_space, act_space, device)  # (HARL_TRPO_CAT_WIDE=1: n > 512, 256-wide and non-ReLU are refused there)
         if self.actor.cat_wide and self.actor.recurrent and self.actor.gru_wide:
             raise NotImplementedError(CAT_WIDE_REFUSALS["hatrpo_gru_wide"])

@@ -23,7 +23,8 @@ import torch.nn as nn
 from . import _lib
 from . import graphs as _graphs
 from ._lib import DHEAD_LD, PS_STRIDE, SLAB, call, ptr, stream
-from .configs import CAT_WIDE_REFUSALS, GAUSS_WIDE_REFUSALS, bwd_k64, bwd_streams, gauss_wide_enabled, gauss_wide_reason, gru_dw6, trunk_dw_stream
+from .configs import (CAT_WIDE_REFUSALS, GAUSS_WIDE_REFUSALS, bwd_k64, bwd_streams, gauss_wide_enabled, gauss_wide_reason, gru_dw6,
+                      is_mixed_256, mixed_256_enabled, mixed_256_reason, trunk_dw_stream)
 
 SUPPORTED_WIDTHS = (64, 128, 256)
 # models_tools.py:28-50; ids of csrc/elementwise.hip (0 = the fused ReLU kernels)
@@ -175,9 +176,15 @@ class _FlatNet(nn.Module):
         for h in self.hidden_sizes:
             if h not in SUPPORTED_WIDTHS:
                 raise NotImplementedError(f"hidden width {h}: kernels are instantiated for {SUPPORTED_WIDTHS}")
-        # width 256 runs on the panel kernels (csrc/panel.hip): every layer 256 wide, feed-forward, inputs up to 512
+        # width 256 runs on the panel kernels (csrc/panel.hip): every layer 256 wide, feed-forward, inputs up to 512 -- or, under
+        # HARL_MIXED_256=1, 256-wide layers next to 64- / 128-wide ones on the same layer-by-layer route (csrc/rect.hip)
         self.panel = 256 in self.hidden_sizes
-        if self.panel and (any(h != 256 for h in self.hidden_sizes) or self.recurrent or in_dim > 512):
+        self.mixed_256 = is_mixed_256(self.hidden_sizes) and mixed_256_enabled()
+        if self.mixed_256:
+            why = mixed_256_reason(self.hidden_sizes, self.activation_func, self.recurrent, in_dim)
+            if why is not None:
+                raise NotImplementedError(why)
+        elif self.panel and (any(h != 256 for h in self.hidden_sizes) or self.recurrent or in_dim > 512):
             raise NotImplementedError("hidden width 256: all layers must be 256 wide, feed-forward, inputs <= 512")
         if self.act_id and (self.recurrent or self.panel or in_dim > 512):
             raise NotImplementedError("activation functions other than relu: feed-forward MLPs of width 64 / 128 with inputs <= 512")
@@ -640,12 +647,15 @@ class _FlatNet(nn.Module):
                 call("harl_act_ln_fwd", ptr(self.zraw), M, h, self.act_id, ptr(self.xh[l]), ptr(self.amean[l]), ptr(self.rstd[l]),
                      s, tag="act_ln_fwd")
             return
-        if route.kind == "panel":  # width 256: x0n image -> panel GEMMs (csrc/panel.hip)
+        if route.kind == "panel":  # width 256: x0n image -> panel GEMMs (csrc/panel.hip; csrc/rect.hip for a narrower output)
             for l in range(len(hs)):
                 Wp, bp = self._packs[l]
-                xin, kp, d = (self.x0n, self.kp0, self.in_dim) if l == 0 else (self.xh[l - 1], 256, 256)
-                call("harl_mlp_panel_fwd", ptr(xin), M, kp, ptr(Wp), d, ptr(bp), 256, ptr(self.xh[l]), ptr(self.rmask[l]),
-                     ptr(self.rstd[l]), s, tag="fwd_panel")
+                xin, kp, d = (self.x0n, self.kp0, self.in_dim) if l == 0 else (self.xh[l - 1], hs[l - 1], hs[l - 1])
+                # (the first layer and 256 -> 256 as on all-256 trunks; every other pair of widths on the rectangular kernel)
+                square = hs[l] == 256 and (l == 0 or hs[l - 1] == 256)
+                name, tag = ("harl_mlp_panel_fwd", "fwd_panel") if square else ("harl_mlp_rect_fwd", "fwd_rect")
+                call(name, ptr(xin), M, kp, ptr(Wp), d, ptr(bp), hs[l], ptr(self.xh[l]), ptr(self.rmask[l]),
+                     ptr(self.rstd[l]), s, tag=tag)
             return
         if route.kind == "trunk":
             # every layer (+ the input half of a fused GRU's gates) in ONE launch; forward-only passes write nothing but what
@@ -858,7 +868,7 @@ class _FlatNet(nn.Module):
             fx, _, _, fh = self.feat()
             if self.wide_head:  # ATL(64) image: an ordinary two-operand weight-gradient GEMM (partial layout dWp[64][fh] | dbp[64])
                 self._dw_atl(self.dhead, 64, fx, fh, M, -1, s, "dw_head")
-            elif self.panel:  # 256-wide trunk (HATRPO's separate head-gradient pass; HAPPO's loss kernel fuses it)
+            elif self.panel and fh == 256:  # 256-wide last layer (HATRPO's separate head-gradient pass; HAPPO's loss kernel fuses it)
                 call("harl_head_dw_rows256", ptr(self.dhead), M, self._layers()[-1][4], ptr(fx), ptr(self.part[self._part_offs[-1]:]),
                      self.n_wg, s, tag="dw_head")
             else:
@@ -898,15 +908,17 @@ class _FlatNet(nn.Module):
         return 1
 
     def _backward_panel(self, M: int, s) -> None:
-        """Width 256 (csrc/panel.hip): per layer dW = dz^T x_hat_prev, then dz_prev through the panel GEMM."""
-        cur = 0
-        for l in range(len(self.hidden_sizes) - 1, -1, -1):
-            b_in, k_in = (self.x0n, self.kp0) if l == 0 else (self.xh[l - 1], 256)
-            self._dw_atl(self.dz[cur], 256, b_in, k_in, M, l, s, "dw_hidden" if l else "dw_input")
+        """Width 256 (csrc/panel.hip; csrc/rect.hip where one side of a layer is narrower): per layer dW = dz^T x_hat_prev, then
+        dz_prev through the panel GEMM."""
+        hs, cur = self.hidden_sizes, 0
+        for l in range(len(hs) - 1, -1, -1):
+            b_in, k_in = (self.x0n, self.kp0) if l == 0 else (self.xh[l - 1], hs[l - 1])
+            self._dw_atl(self.dz[cur], hs[l], b_in, k_in, M, l, s, "dw_hidden" if l else "dw_input")
             if l > 0:
                 Wp, _ = self._packs[l]
-                call("harl_mlp_panel_bwd", ptr(self.dz[cur]), ptr(self.xh[l - 1]), ptr(self.rmask[l - 1]),
-                     ptr(self.rstd[l - 1]), M, 256, 256, ptr(Wp), ptr(self.dz[1 - cur]), s, tag="bwd_panel")
+                name, tag = ("harl_mlp_panel_bwd", "bwd_panel") if hs[l] == hs[l - 1] == 256 else ("harl_mlp_rect_bwd", "bwd_rect")
+                call(name, ptr(self.dz[cur]), ptr(self.xh[l - 1]), ptr(self.rmask[l - 1]),
+                     ptr(self.rstd[l - 1]), M, hs[l], hs[l - 1], ptr(Wp), ptr(self.dz[1 - cur]), s, tag=tag)
                 cur = 1 - cur
 
     def _backward_act(self, M: int, s) -> None:
@@ -1179,6 +1191,10 @@ class StochasticPolicy(_FlatNet):
         if not self.grouped and not self.gauss_wide and (self.act_dim > 64 or (self.act_dim > 32 and not self.discrete)):
             raise NotImplementedError("action heads wider than 32 (Categorical: 64) are not instantiated")
         self.wide_head = (not self.grouped) and self.act_dim > 32
+        if self.mixed_256 and self.wide_head:  # (the head kernels of a 256-wide last layer stop at 32 outputs)
+            why = mixed_256_reason(self.hidden_sizes, head=self.act_dim)
+            if why is not None:
+                raise NotImplementedError(why)
         self._finalize_params()
         self.fold()
 

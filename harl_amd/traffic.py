@@ -282,6 +282,8 @@ ALGORITHMIC_BYTES: Dict[str, Callable[[Sequence], float]] = {
     "harl_gae_returns": _gae,
     "harl_mlp_panel_fwd": _panel_fwd,
     "harl_mlp_panel_bwd": _panel_bwd,
+    "harl_mlp_rect_fwd": _panel_fwd,  # (csrc/rect.hip: the same arguments, the same bytes per row)
+    "harl_mlp_rect_bwd": _panel_bwd,
     "harl_cat_head_logp": _cat_head_logp,
     "harl_cat_head_loss": _cat_head_loss,
     "harl_cat_head_fvp": _cat_head_fvp,
@@ -407,6 +409,8 @@ ALGORITHMIC_FLOPS: Dict[str, Callable[[Sequence], float]] = {
     "harl_mlp_bwd_trunk": _f_bwd_trunk,
     "harl_mlp_panel_fwd": lambda a: 2.0 * a[1] * a[4] * a[6],
     "harl_mlp_panel_bwd": lambda a: 2.0 * a[4] * a[5] * a[6],
+    "harl_mlp_rect_fwd": lambda a: 2.0 * a[1] * a[4] * a[6],
+    "harl_mlp_rect_bwd": lambda a: 2.0 * a[4] * a[5] * a[6],
     "harl_gru_fwd": _f_gru_fwd,
     "harl_gru_bwd": _f_gru_bwd,
     "harl_actor_head_loss": lambda a: _f_head(a[3], a[4], a[11], True) - (2.0 * a[3] * a[11] * a[4] if not a[30] else 0.0),

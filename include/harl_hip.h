@@ -197,6 +197,18 @@ int harl_mlp_panel_tangent(const float *xin_dot, const float *xin, long M, int K
                            float *xout_dot, void *stream);
 int harl_mlp_panel_bwd(const float *dz, const float *xprev, const uint32_t *relu_mask_prev, const float *rstd_prev, long M,
                        int HO, int HI, const float *Wp, float *dz_prev, void *stream);
+/* Layers between a 256-wide side and a narrower one (csrc/rect.hip; the reference's MLPBase builds any hidden_sizes list,
+ * mlp.py:7-70 -- [256, 128], [128, 256], [256, 128, 64]; opt-in HARL_MIXED_256=1).  The K-panel walk of the kernels above with
+ * 2 / 4 / 8 output row tiles and 128 / 64 / 32 columns per panel; records in the layouts of the 64 / 128 / 256-wide kernels.
+ *   harl_mlp_rect_fwd: xout = norm(relu(Wp xin + bp)), xin = ATL(KP) image (KP a multiple of 32, D <= KP <= 512: x0n of
+ *     harl_mlp_x0n_wide, or x_hat of the layer before with KP = D), Wp [HO][D] row-major, HO = 64 / 128 / 256.
+ *   harl_mlp_rect_bwd: dz_prev = relu' . LNbwd(Wp^T dz), Wp [HO][HI], HO and HI each 64 / 128 / 256 (the role of
+ *     harl_mlp_bwd_dx).  Rows past M of the last slab: dz_prev is 0 where dz is.
+ * Other shapes: -2 and an error text.  Weight gradients: harl_mlp_dw_partials(a_kind = 0). */
+int harl_mlp_rect_fwd(const float *xin, long M, int KP, const float *Wp, int D, const float *bp, int HO, float *xout,
+                      uint32_t *relu_mask, float *rstd, void *stream);
+int harl_mlp_rect_bwd(const float *dz, const float *xprev, const uint32_t *relu_mask_prev, const float *rstd_prev, long M,
+                      int HO, int HI, const float *Wp, float *dz_prev, void *stream);
 /* the same two layers FROM the x0n ATL(32 | 64) image of harl_mlp_x0n_wide (D <= 64; identity row order; the image is
  * built once per buffer): no gather, no input-LayerNorm work per call */
 int harl_mlp_fwd_fused2x(const float *x0n, long M, const float *W1p, int D, const float *b1p, const float *W2p,
