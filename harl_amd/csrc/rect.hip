@@ -27,6 +27,8 @@
 //             is written while others still read panel p, one barrier per panel (8 per slab where k_panel has 16).
 //   forward  : x_hat_out = norm(relu(W' x_in + b'))            x_in = ATL(KP) image, KP a multiple of 32 up to 512
 //   backward : dz_in = relu' . LNbwd(W'^T dz_out)               (HI, HO) over {64, 128, 256}^2
+//   tangent  : x_out_dot = LNjac(mask . (W'_dot x_in + b'_dot [+ W' x_in_dot]))   HATRPO's Fisher-vector product on these trunks
+//              (opt-in HARL_TRPO_MIXED_256=1): both products are ONE stream of sub-panels through the same prefetch pipeline
 // The GEMM is split_mfma.h's exact three-term bf16 split, six products, fp32 accumulation; x_hat / ReLU mask words / rstd
 // leave in the layouts of the 64 / 128-wide layer kernels (fwd_epilogue.h) and of k_panel, so the head kernels,
 // harl_mlp_dw_partials and harl_mlp_bwd_dx read them unchanged.  Rows past M inside the last slab are computed like any
@@ -53,24 +55,42 @@ constexpr int PER_THREAD = PANEL_FRAGS / WG_THREADS;  // 4 fragments = 32 fp32 w
 // Addresses: fragment u of a thread differs from its fragment 0 by a whole sub-panel or by whole row tiles, and register c of
 // a fragment by the constant feat_base(c), so every load is (scalar base of (u, c)) + ONE lane offset per thread -- 32 lane
 // addresses would otherwise stay live across the panel loop, next to the accumulators of two waves per SIMD.
-template <int MT, bool TRANSPOSED>
-__device__ __forceinline__ void load_panel(float (&w)[PER_THREAD][8], const float *__restrict__ Wp, int ldw, int kvalid, int p,
-                                           int nsub) {
+// TWO (the tangent's two-operand reduction): the reduction is ONE stream of sub-panels, of which the first n_first belong to
+// (Wp, ldw, kvalid) and the following ones to the second matrix (W2 = [32 MT][ld2], every column valid).  Which of the two a
+// sub-panel reads is workgroup-uniform, so it costs scalar selects and one more lane offset per thread; a panel may hold
+// sub-panels of both.  TWO = false never looks at the three extra arguments.
+template <int MT, bool TRANSPOSED, bool TWO>
+__device__ __forceinline__ void load_panel(float (&w)[PER_THREAD][8], const float *__restrict__ Wp, int ldw, int kvalid,
+                                           const float *__restrict__ W2, int ld2, int n_first, int p, int nsub) {
+  static_assert(!(TWO && TRANSPOSED), "the two-operand stream is a forward-form reduction");
   constexpr int SUB = MT * 128, NSUB = 8 / MT;
   const int r0 = threadIdx.x % SUB, ln = r0 & 63, j = (r0 >> 6) & 1, m0 = 32 * (r0 >> 7) + (ln & 31), kl = 16 * j + 4 * (ln >> 5);
   const unsigned voff = TRANSPOSED ? (unsigned)(kl * ldw + m0) : (unsigned)(m0 * ldw + kl);
+  const unsigned voff2 = TWO ? (unsigned)(m0 * ld2 + kl) : 0u;
 #pragma unroll
   for (int u = 0; u < PER_THREAD; ++u) {
     const int sub = (u * WG_THREADS) / SUB;          // (compile time per u: 256 threads never straddle a sub-panel)
     const int dm = 32 * (((u * WG_THREADS) % SUB) >> 7);  // ... and this fragment's rows are dm below those of fragment 0
-    const int ks = 32 * (p * NSUB + sub);
+    int g = p * NSUB + sub;                          // the sub-panel's place in the stream, then in its own matrix
+    const float *Wm = Wp;
+    int ld = ldw, kv = kvalid;
+    unsigned vo = voff;
+    if constexpr (TWO) {
+      if (g >= n_first) {  // (workgroup-uniform)
+        g -= n_first;
+        Wm = W2;
+        ld = kv = ld2;
+        vo = voff2;
+      }
+    }
+    const int ks = 32 * g;
     if (sub < nsub) {  // (workgroup-uniform)
 #pragma unroll
       for (int c = 0; c < 8; ++c) {
         const int kc = ks + feat_base(c);  // k = kc + kl
-        const float *base = TRANSPOSED ? Wp + (kc * ldw + dm) : Wp + (dm * ldw + kc);
-        const bool in = kc + kl < kvalid;
-        const float v = base[in ? voff : 0u];
+        const float *base = TRANSPOSED ? Wm + (kc * ld + dm) : Wm + (dm * ld + kc);
+        const bool in = kc + kl < kv;
+        const float v = base[in ? vo : 0u];
         w[u][c] = in ? v : 0.f;
       }
     } else {
@@ -97,8 +117,17 @@ __device__ __forceinline__ void commit_panel(u32x4 *__restrict__ buf, const floa
   }
 }
 
-// the slab's 32 columns of sub-panel s: pieces 4 s .. 4 s + 3 of its ATL(KP) image (xp = the slab's image + lane)
-__device__ __forceinline__ void load_cols(const f32x4 *__restrict__ xp, int s, float (&x)[16]) {
+// the slab's 32 columns of sub-panel s: pieces 4 s .. 4 s + 3 of its ATL(KP) image (xp = the slab's image + lane).  TWO: from
+// sub-panel n_first on, pieces 4 (s - n_first) .. of the slab's second image xp2 (load_panel's stream)
+template <bool TWO>
+__device__ __forceinline__ void load_cols(const f32x4 *__restrict__ xp, const f32x4 *__restrict__ xp2, int n_first, int s,
+                                          float (&x)[16]) {
+  if constexpr (TWO) {
+    if (s >= n_first) {  // (workgroup-uniform)
+      s -= n_first;
+      xp = xp2;
+    }
+  }
 #pragma unroll
   for (int q = 0; q < 4; ++q) {
     const f32x4 v = xp[(4 * s + q) * WAVE];
@@ -118,24 +147,31 @@ __device__ __forceinline__ T *per_iteration(T *p) {
   return p;
 }
 
-// MODE 0 forward, 1 backward
+// MODE 0 forward, 1 backward, 2 forward-mode tangent (HATRPO's Fisher-vector product):
+//   z_dot = Wp (= W'_dot) x_in + bp (= b'_dot) [+ W2 (= W') x_in2 (= x_in_dot)],  x_out_dot = LNjac(mask . z_dot) with the PRIMAL
+//   x_hat / mask / rstd of this layer in xprev / mask_prev / rstd_prev.  The two products are one stream of n_first + ld2 / 32
+//   sub-panels (load_panel): the prefetch / commit pipeline below never learns where one operand ends, a panel may straddle the
+//   boundary (MT = 2, 64 -> 64: the whole K = 128 reduction is ONE panel), and there is no drain between the operands.  n_first
+//   counts the sub-panels that hold a valid column of Wp; the columns of x_in past them would meet zero weights and are skipped.
 template <int MT, int MODE>
 __global__ __launch_bounds__(WG_THREADS, MT == 8 ? 1 : 2) void k_panel_rect(
     const float *__restrict__ xin, int KP, const float *__restrict__ Wp, int ldw, int kvalid, const float *__restrict__ bp,
     float *__restrict__ xout, uint32_t *__restrict__ mask_out, float *__restrict__ rstd_out, const float *__restrict__ xprev,
-    const uint32_t *__restrict__ mask_prev, const float *__restrict__ rstd_prev, long n_slabs) {
-  constexpr bool BWD = MODE == 1;
+    const uint32_t *__restrict__ mask_prev, const float *__restrict__ rstd_prev, long n_slabs,
+    const float *__restrict__ xin2 = nullptr, const float *__restrict__ W2 = nullptr, int ld2 = 0, int n_first = 0) {
+  constexpr bool BWD = MODE == 1, TWO = MODE == 2;
   constexpr int H = 32 * MT, NSUB = 8 / MT, NBUF = MT == 8 ? 2 : 1, SUB = MT * 128, BUF = 3 * PANEL_FRAGS;
   extern __shared__ __attribute__((aligned(16))) float lds[];
   u32x4 *img = reinterpret_cast<u32x4 *>(lds);
   const int lane = threadIdx.x & 63, wave = wave_id(), i = lane & 31, h = lane >> 5;
-  const int n_sub = KP / 32, n_panels = (n_sub + NSUB - 1) / NSUB;
+  const int n_sub = TWO ? n_first + (xin2 ? ld2 / 32 : 0) : KP / 32, n_panels = (n_sub + NSUB - 1) / NSUB;
   const long n_iter = (n_slabs + WAVES_PER_WG - 1) / WAVES_PER_WG;
   for (long it = blockIdx.x; it < n_iter; it += gridDim.x) {  // uniform trip count: barriers inside
     const long s_raw = it * WAVES_PER_WG + wave;
     const bool live = s_raw < n_slabs;
     const long slab = live ? s_raw : n_slabs - 1;
     const f32x4 *xp = reinterpret_cast<const f32x4 *>(xin + slab * (long)KP * SLAB) + lane;
+    const f32x4 *xp2 = TWO ? reinterpret_cast<const f32x4 *>(xin2 + slab * (long)ld2 * SLAB) + lane : nullptr;  // (never read without xin2)
     f32x16 acc[MT];
     // (the bias is read again every iteration: hoisted out of this loop it would hold 16 MT registers for the kernel's lifetime)
     const float *bpi = per_iteration(bp);
@@ -145,17 +181,17 @@ __global__ __launch_bounds__(WG_THREADS, MT == 8 ? 1 : 2) void k_panel_rect(
       for (int r = 0; r < 16; ++r) acc[t][r] = BWD ? 0.f : bpi[32 * t + (r & 3) + 8 * (r >> 2) + 4 * h];
     float w[PER_THREAD][8];
     int nsub_p = n_sub < NSUB ? n_sub : NSUB;
-    load_panel<MT, BWD>(w, Wp, ldw, kvalid, 0, nsub_p);
+    load_panel<MT, BWD, TWO>(w, Wp, ldw, kvalid, W2, ld2, n_first, 0, nsub_p);
     __syncthreads();  // the last panel of the iteration before is no longer being read
     commit_panel<MT>(img, w, nsub_p);
     for (int p = 0; p < n_panels; ++p) {
       // this slab's columns of the panel's first sub-panel, then the prefetch; the columns of sub-panel s + 1 are asked for
       // while sub-panel s multiplies (by then the prefetch in front of them has long returned)
       float xa[16];
-      load_cols(xp, p * NSUB, xa);
+      load_cols<TWO>(xp, xp2, n_first, p * NSUB, xa);
       const bool more = p + 1 < n_panels;
       const int rest = n_sub - (p + 1) * NSUB, nsub_next = rest < NSUB ? rest : NSUB;
-      if (more) load_panel<MT, BWD>(w, Wp, ldw, kvalid, p + 1, nsub_next);
+      if (more) load_panel<MT, BWD, TWO>(w, Wp, ldw, kvalid, W2, ld2, n_first, p + 1, nsub_next);
       __syncthreads();  // panel p is complete (and, with two buffers, panel p - 1 is no longer being read)
       const u32x4 *wl = img + (p % NBUF) * BUF + lane;
 #pragma unroll
@@ -164,7 +200,7 @@ __global__ __launch_bounds__(WG_THREADS, MT == 8 ? 1 : 2) void k_panel_rect(
           u32x4 x1[2], x2[2], x3[2];
           split_acts<16>(xa, x1, x2, x3);
           float xb[16];
-          if (sub + 1 < nsub_p) load_cols(xp, p * NSUB + sub + 1, xb);
+          if (sub + 1 < nsub_p) load_cols<TWO>(xp, xp2, n_first, p * NSUB + sub + 1, xb);
           split_gemm<MT, 2>(wl + sub * 3 * SUB, x1, x2, x3, acc, [](int) {});
           if (sub + 1 < nsub_p) {
 #pragma unroll
@@ -180,7 +216,27 @@ __global__ __launch_bounds__(WG_THREADS, MT == 8 ? 1 : 2) void k_panel_rect(
     if (!live) continue;
     constexpr int NR = H / 2, NW = (NR + 31) / 32;
     float *xo = per_iteration(xout);
-    if constexpr (!BWD) {
+    if constexpr (TWO) {  // mlp.hip's ln_jac_store on registers: nothing of it is addressed before the panel loop has ended
+      float xh[NR], ad[NR];
+      atl_load<H>(per_iteration(xprev), slab, lane, xh);
+      const uint32_t *mi = per_iteration(mask_prev);
+      uint32_t bits[NW];
+#pragma unroll
+      for (int wd = 0; wd < NW; ++wd) bits[wd] = mi[(slab * NW + wd) * WAVE + lane];
+      const float rstd = per_iteration(rstd_prev)[slab * SLAB + i];
+      float s1 = 0.f, s2 = 0.f;
+#pragma unroll
+      for (int R = 0; R < NR; ++R) {
+        ad[R] = mask_pop(acc[R >> 4][R & 15], bits[R >> 5]);
+        s1 += ad[R];
+        s2 += ad[R] * xh[R];
+      }
+      s1 = wave_sum32(s1) * (1.0f / H);
+      s2 = wave_sum32(s2) * (1.0f / H);
+#pragma unroll
+      for (int R = 0; R < NR; ++R) ad[R] = rstd * (ad[R] - s1 - xh[R] * s2);
+      atl_store<H>(xo, slab, lane, ad);
+    } else if constexpr (!BWD) {
       uint32_t *mo = per_iteration(mask_out);
       float *ro = per_iteration(rstd_out);
       uint32_t bits[NW];
@@ -223,12 +279,12 @@ __global__ __launch_bounds__(WG_THREADS, MT == 8 ? 1 : 2) void k_panel_rect(
 template <int MT, int MODE>
 void launch_rect(const float *xin, int KP, const float *Wp, int ldw, int kvalid, const float *bp, float *xout,
                  uint32_t *mask_out, float *rstd_out, const float *xprev, const uint32_t *mask_prev, const float *rstd_prev,
-                 long n_slabs, hipStream_t s) {
+                 long n_slabs, hipStream_t s, const float *xin2 = nullptr, const float *W2 = nullptr, int ld2 = 0, int n_first = 0) {
   constexpr int NBUF = MT == 8 ? 2 : 1, WG_PER_CU = MT == 8 ? 1 : 2;
   const size_t shm = (size_t)NBUF * 3 * PANEL_FRAGS * sizeof(u32x4);
   allow_big_lds(k_panel_rect<MT, MODE>, shm);
   hipLaunchKernelGGL((k_panel_rect<MT, MODE>), dim3(persistent_grid(n_slabs, WG_PER_CU)), dim3(WG_THREADS), shm, s, xin, KP, Wp,
-                     ldw, kvalid, bp, xout, mask_out, rstd_out, xprev, mask_prev, rstd_prev, n_slabs);
+                     ldw, kvalid, bp, xout, mask_out, rstd_out, xprev, mask_prev, rstd_prev, n_slabs, xin2, W2, ld2, n_first);
 }
 
 bool width_ok(int h) { return h == 64 || h == 128 || h == 256; }
@@ -256,4 +312,22 @@ extern "C" int harl_mlp_rect_bwd(const float *dz, const float *xprev, const uint
   if (HI == 64) RECT(2); else if (HI == 128) RECT(4); else RECT(8);
 #undef RECT
   return check_launch("harl_mlp_rect_bwd");
+}
+
+extern "C" int harl_mlp_rect_tangent(const float *xin_dot, const float *xin, long M, int KP, int HO, const float *Wp,
+                                     const float *Wdp, int D, const float *bdp, const float *xprimal, const uint32_t *mask_in,
+                                     const float *rstd_in, float *xout_dot, void *stream) {
+  if (M <= 0) return 0;
+  if (!width_ok(HO)) return bad("harl_mlp_rect_tangent: output width must be 64, 128 or 256");
+  if (xin_dot) {
+    if (!Wp || !width_ok(KP) || D != KP) return bad("harl_mlp_rect_tangent: a hidden layer (x_in_dot given) has KP = D = 64, 128 or 256 and needs W'");
+  } else if (D < 1 || KP % 32 != 0 || KP < D || KP > 512 || HO == 256) {
+    return bad("harl_mlp_rect_tangent: a first layer has KP a multiple of 32, >= D >= 1 and <= 512, and 64 or 128 outputs");
+  }
+  const long n_slabs = n_slabs_of(M);
+  // the stream: (D + 31) / 32 sub-panels of W'_dot x_in, then KP / 32 of W' x_in_dot (both matrices [HO][D])
+#define RECT(MTv) launch_rect<MTv, 2>(xin, KP, Wdp, D, D, bdp, xout_dot, nullptr, nullptr, xprimal, mask_in, rstd_in, n_slabs, (hipStream_t)stream, xin_dot, xin_dot ? Wp : nullptr, xin_dot ? KP : 0, (D + 31) / 32)
+  if (HO == 64) RECT(2); else if (HO == 128) RECT(4); else RECT(8);
+#undef RECT
+  return check_launch("harl_mlp_rect_tangent");
 }

@@ -19,7 +19,7 @@ from . import _lib
 from ._lib import call, ptr, stream
 from .buffers import OnPolicyActorBuffer, consume_randperm, rng_sync
 from .configs import (CAT_WIDE_REFUSALS, GAUSS_WIDE_REFUSALS, MIXED_256_REFUSALS, gauss_wide_enabled, is_mixed_256,
-                      mixed_256_enabled, trpo_cat_wide_enabled)
+                      mixed_256_enabled, trpo_cat_wide_enabled, trpo_mixed_256_enabled)
 from .happo import OnPolicyBase
 from .nets import build_seq, consume_policy_init_rng, seq_compact
 from .valuenorm import _as_dev
@@ -34,8 +34,8 @@ class HATRPO(OnPolicyBase):
         if act_space.__class__.__name__ == "Box" and int(act_space.shape[0]) > 32 and gauss_wide_enabled():
             # (harl_actor_head_fvp, harl_trpo_begin and the line search read the log_std block from the scalar row)
             raise NotImplementedError(GAUSS_WIDE_REFUSALS["hatrpo" if int(act_space.shape[0]) <= 64 else "n"])
-        if is_mixed_256(list(args["hidden_sizes"])) and mixed_256_enabled():  # (the tangent pass: harl_mlp_panel_tangent)
-            raise NotImplementedError(MIXED_256_REFUSALS["hatrpo"])
+        if is_mixed_256(list(args["hidden_sizes"])) and mixed_256_enabled() and not trpo_mixed_256_enabled():
+            raise NotImplementedError(MIXED_256_REFUSALS["hatrpo"])  # (the tangent of a rectangular pair is opt-in: _fvp)
         super().__init__(args, obs_space, act_space, device)  # (HARL_TRPO_CAT_WIDE=1: n > 512, 256-wide and non-ReLU are refused there)
         if self.actor.cat_wide and self.actor.recurrent and self.actor.gru_wide:
             raise NotImplementedError(CAT_WIDE_REFUSALS["hatrpo_gru_wide"])
@@ -143,13 +143,24 @@ class HATRPO(OnPolicyBase):
                 call("harl_act_ln_tangent", ptr(zd1), ptr(zd2), ptr(net.xh[l]), ptr(net.amean[l]), ptr(net.rstd[l]), m, hs[l],
                      net.act_id, ptr(ws["xd"][l]), s, tag="act_ln_tangent")
         elif net.panel:  # width 256 (csrc/panel.hip, round 4): the same K-panel walk with the LayerNorm Jacobian as epilogue
-            call("harl_mlp_panel_tangent", None, ptr(net.x0n), m, net.kp0, None, ptr(Wpd), net.in_dim, ptr(bpd), ptr(net.xh[0]),
-                 ptr(net.rmask[0]), ptr(net.rstd[0]), ptr(ws["xd"][0]), s, tag="tangent_panel")
+            # (the first layer into 256 and 256 -> 256 as on all-256 trunks; every other pair of widths -- HARL_TRPO_MIXED_256=1 --
+            # on the rectangular kernel, csrc/rect.hip)
+            if hs[0] == 256:
+                call("harl_mlp_panel_tangent", None, ptr(net.x0n), m, net.kp0, None, ptr(Wpd), net.in_dim, ptr(bpd), ptr(net.xh[0]),
+                     ptr(net.rmask[0]), ptr(net.rstd[0]), ptr(ws["xd"][0]), s, tag="tangent_panel")
+            else:
+                call("harl_mlp_rect_tangent", None, ptr(net.x0n), m, net.kp0, hs[0], None, ptr(Wpd), net.in_dim, ptr(bpd),
+                     ptr(net.xh[0]), ptr(net.rmask[0]), ptr(net.rstd[0]), ptr(ws["xd"][0]), s, tag="tangent_rect")
             for l in range(1, L):
                 Wp, _ = net._packs[l]
                 Wpd, bpd = packs_d[l]
-                call("harl_mlp_panel_tangent", ptr(ws["xd"][l - 1]), ptr(net.xh[l - 1]), m, 256, ptr(Wp), ptr(Wpd), 256, ptr(bpd),
-                     ptr(net.xh[l]), ptr(net.rmask[l]), ptr(net.rstd[l]), ptr(ws["xd"][l]), s, tag="tangent_panel")
+                if hs[l] == hs[l - 1] == 256:
+                    call("harl_mlp_panel_tangent", ptr(ws["xd"][l - 1]), ptr(net.xh[l - 1]), m, 256, ptr(Wp), ptr(Wpd), 256, ptr(bpd),
+                         ptr(net.xh[l]), ptr(net.rmask[l]), ptr(net.rstd[l]), ptr(ws["xd"][l]), s, tag="tangent_panel")
+                else:
+                    call("harl_mlp_rect_tangent", ptr(ws["xd"][l - 1]), ptr(net.xh[l - 1]), m, hs[l - 1], hs[l], ptr(Wp), ptr(Wpd),
+                         hs[l - 1], ptr(bpd), ptr(net.xh[l]), ptr(net.rmask[l]), ptr(net.rstd[l]), ptr(ws["xd"][l]), s,
+                         tag="tangent_rect")
         elif net.wide:  # x0n of the same rows is still there from the forward pass of _surrogate()
             call("harl_mlp_tangent_wide", ptr(net.x0n), m, net.kp0, ptr(Wpd), net.in_dim, ptr(bpd), hs[0], ptr(net.w1img),
                  ptr(net.xh[0]), ptr(net.rmask[0]), ptr(net.rstd[0]), ptr(ws["xd"][0]), s, tag="tangent_wide")

@@ -244,6 +244,12 @@ def _tangent_hidden(a: Sequence) -> float:
     return a[2] * (2 * 4.0 * a[3] + _act(a[4]) + 4.0 * a[4])
 
 
+def _tangent_rect(a: Sequence) -> float:
+    # (xin_dot, xin, M, KP, HO, Wp, Wdp, D, bdp, xprimal, mask_in, rstd_in, xout_dot, stream), tag tangent_rect: the input image
+    # (and its tangent, for a hidden layer), the primal x_hat / mask / rstd of the layer, the tangent out
+    return a[2] * (4.0 * a[3] * (2 if a[0] else 1) + _act(a[4]) + 4.0 * a[4])
+
+
 def _gae(a: Sequence) -> float:
     # rewards, value_preds (T+1), masks (T+1), bad_masks (T+1) in; returns (T+1), advantages out
     T, n = a[8], a[9]
@@ -284,6 +290,7 @@ ALGORITHMIC_BYTES: Dict[str, Callable[[Sequence], float]] = {
     "harl_mlp_panel_bwd": _panel_bwd,
     "harl_mlp_rect_fwd": _panel_fwd,  # (csrc/rect.hip: the same arguments, the same bytes per row)
     "harl_mlp_rect_bwd": _panel_bwd,
+    "harl_mlp_rect_tangent": _tangent_rect,
     "harl_cat_head_logp": _cat_head_logp,
     "harl_cat_head_loss": _cat_head_loss,
     "harl_cat_head_fvp": _cat_head_fvp,
@@ -411,6 +418,7 @@ ALGORITHMIC_FLOPS: Dict[str, Callable[[Sequence], float]] = {
     "harl_mlp_panel_bwd": lambda a: 2.0 * a[4] * a[5] * a[6],
     "harl_mlp_rect_fwd": lambda a: 2.0 * a[1] * a[4] * a[6],
     "harl_mlp_rect_bwd": lambda a: 2.0 * a[4] * a[5] * a[6],
+    "harl_mlp_rect_tangent": lambda a: 2.0 * (2 if a[0] else 1) * a[2] * a[7] * a[4],  # one GEMM for a first layer, two for a hidden one
     "harl_gru_fwd": _f_gru_fwd,
     "harl_gru_bwd": _f_gru_bwd,
     "harl_actor_head_loss": lambda a: _f_head(a[3], a[4], a[11], True) - (2.0 * a[3] * a[11] * a[4] if not a[30] else 0.0),

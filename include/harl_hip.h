@@ -209,6 +209,19 @@ int harl_mlp_rect_fwd(const float *xin, long M, int KP, const float *Wp, int D, 
                       uint32_t *relu_mask, float *rstd, void *stream);
 int harl_mlp_rect_bwd(const float *dz, const float *xprev, const uint32_t *relu_mask_prev, const float *rstd_prev, long M,
                       int HO, int HI, const float *Wp, float *dz_prev, void *stream);
+/* Forward-mode tangent of such a layer (HATRPO's Fisher-vector product, trpo_util.py:132-158 -- the reference's double backward
+ * through MLPBase, mlp.py:7-70 -- on the trunks above; opt-in HARL_TRPO_MIXED_256=1 next to HARL_MIXED_256=1):
+ * x_out_dot = LNjac(mask . (Wdp x_in + bdp [+ Wp x_in_dot])) with the PRIMAL x_hat / mask / rstd of this layer, arguments and
+ * layouts of harl_mlp_panel_tangent plus the output width.  k_panel_rect<MT, 2>: both products are ONE stream of 32-column
+ * sub-panels through the prefetch pipeline of the two kernels above.
+ *   first layer : x_in_dot = NULL, x_in = the x0n image (KP a multiple of 32, 1 <= D <= KP <= 512), HO = 64 / 128 (a first
+ *                 layer into 256 is harl_mlp_panel_tangent's), Wp unused.
+ *   hidden layer: KP = D = 64 / 128 / 256, x_in = x_hat of the layer before, x_in_dot its tangent, Wp the folded weights
+ *                 [HO][D], HO = 64 / 128 / 256.
+ * Other shapes: -2 and an error text.  Rows past M of the last slab are computed like any other, as there. */
+int harl_mlp_rect_tangent(const float *xin_dot, const float *xin, long M, int KP, int HO, const float *Wp, const float *Wdp,
+                          int D, const float *bdp, const float *xprimal, const uint32_t *mask_in, const float *rstd_in,
+                          float *xout_dot, void *stream);
 /* the same two layers FROM the x0n ATL(32 | 64) image of harl_mlp_x0n_wide (D <= 64; identity row order; the image is
  * built once per buffer): no gather, no input-LayerNorm work per call */
 int harl_mlp_fwd_fused2x(const float *x0n, long M, const float *W1p, int D, const float *b1p, const float *W2p,

@@ -126,6 +126,18 @@ def main():
         ("h17_bwd_dx", lambda: call("harl_mlp_bwd_dx", ptr(xa), ptr(xb), ptr(mask2_), ptr(rstd2_), B2, H, H, ptr(W), ptr(xo), None, 0, None, 0, s), GB(B2 * (1536 + 20))),
         ("h17_dw_hidden", lambda: call("harl_mlp_dw_partials", ptr(xa), 0, 0, H, ptr(xb), 0, 0, None, None, None, H, B2, ptr(part), n_wg, s), GB(B2 * 1024)),
     ]
+    # ---- the same rows on layers with a 256-wide side: the tangent of a rectangular pair (k_panel_rect<MT, 2>, one stream of
+    # sub-panels) next to k_panel<2> (one walk per operand) at 256 -> 256, the one shape both take
+    ya, yb, yc, yo = rn(mp2 * 256), rn(mp2 * 256), rn(mp2 * 256), torch.empty(mp2 * 256, device=dev)
+    Wr, Wrd, br = rn(256 * 256) * 0.06, rn(256 * 256) * 0.06, rn(256) * 0.1
+    mask4_ = mask[:ns2 * 4 * 64]
+    rect = lambda hi, ho: lambda: call("harl_mlp_rect_tangent", ptr(yb), ptr(ya), B2, hi, ho, ptr(Wr), ptr(Wrd), hi, ptr(br), ptr(yc), ptr(mask4_), ptr(rstd2_), ptr(yo), s)  # noqa: E731
+    jobs += [
+        ("h17_tangent_rect_256to128", rect(256, 128), GF(2 * 2.0 * B2 * 256 * 128)),
+        ("h17_tangent_rect_128to256", rect(128, 256), GF(2 * 2.0 * B2 * 128 * 256)),
+        ("h17_tangent_rect_256to256", rect(256, 256), GF(2 * 2.0 * B2 * 256 * 256)),
+        ("h17_tangent_panel_256to256", lambda: call("harl_mlp_panel_tangent", ptr(yb), ptr(ya), B2, 256, ptr(Wr), ptr(Wrd), 256, ptr(br), ptr(yc), ptr(mask4_), ptr(rstd2_), ptr(yo), s), GF(2 * 2.0 * B2 * 256 * 256)),
+    ]
     print(f"B={B}  H={H}  reps={args.reps}  lib={_lib.LIB_PATH}")
     for name, fn, (unit, work) in jobs:
         if args.filters and not any(f in name for f in args.filters):
