@@ -288,6 +288,269 @@ void launch_rect(const float *xin, int KP, const float *Wp, int ldw, int kvalid,
 }
 
 bool width_ok(int h) { return h == 64 || h == 128 || h == 256; }
+
+// ---- grouped heads on these trunks (opt-in HARL_CAT_WIDE_256=1): a Categorical head of 65..512 actions is G <= 4 groups of
+// sp_g = 64 / 128 rows, each a folded pack [sp_g][K], a bias and an ATL(sp_g) image (csrc/cathead.hip).  The two kernels below
+// walk ALL groups in one launch on the machinery above -- sub-panels, the 48 KiB panel, the register prefetch, one slab per wave.
+// The table travels by value in the kernel arguments: every lookup in it is workgroup-uniform and a chain of scalar selects
+// over constant indices (pick / the prefix compares), never an indexed read of a private copy.
+constexpr int MAX_GROUPS = 4;
+struct GroupTab {
+  const float *W[MAX_GROUPS];  // folded pack [sp][ld], ld = the head input's width
+  const float *b[MAX_GROUPS];  // forward: bias [sp]
+  float *img[MAX_GROUPS];      // forward: the ATL(sp) logits image (out); backward: the ATL(sp) dz image (in)
+  int sp[MAX_GROUPS];          // 64 / 128
+  int first[MAX_GROUPS];       // backward: the group's first sub-panel in the K stream (prefix sum of sp / 32; unused: past the end)
+  int n;
+};
+
+template <typename T>
+__device__ __forceinline__ T pick(const T (&a)[MAX_GROUPS], int g) {
+  T v = a[0];
+#pragma unroll
+  for (int k = 1; k < MAX_GROUPS; ++k)
+    if (g == k) v = a[k];
+  return v;
+}
+
+// forward: panel p (two full sub-panels = 64 columns) of ONE group's pack Wm = [rows][ld], as the 128-row panel of MT = 4.  A
+// 64-row group has no rows 64..127: a thread's fragments 1 and 3 are those rows (dm = 64), so they are zeros as a whole and
+// the pack is never read past its end.
+__device__ __forceinline__ void load_panel_rows(float (&w)[PER_THREAD][8], const float *__restrict__ Wm, int ld, int rows, int p) {
+  constexpr int MT = 4, SUB = MT * 128, NSUB = 8 / MT;
+  const int r0 = threadIdx.x % SUB, ln = r0 & 63, j = (r0 >> 6) & 1, m0 = 32 * (r0 >> 7) + (ln & 31), kl = 16 * j + 4 * (ln >> 5);
+  const unsigned voff = (unsigned)(m0 * ld + kl);  // (m0 < 64 <= rows)
+#pragma unroll
+  for (int u = 0; u < PER_THREAD; ++u) {
+    const int sub = (u * WG_THREADS) / SUB, dm = 32 * (((u * WG_THREADS) % SUB) >> 7);  // (compile time: dm = 0 / 64)
+    const bool in = dm < rows;  // (workgroup-uniform; the address stays inside the pack either way)
+    const float *base = Wm + ((in ? dm : 0) * ld + 32 * (p * NSUB + sub));
+#pragma unroll
+    for (int c = 0; c < 8; ++c) {
+      const float v = base[feat_base(c) + voff];
+      w[u][c] = in ? v : 0.f;
+    }
+  }
+}
+
+// z_g = W'_g x + b'_g for every group g, raw (no activation, no LayerNorm): the logits of a grouped head from the ATL(KP) head
+// input, KP = 64 / 128 / 256.  k_panel_rect's forward at MT = 4 with the weight stream running over (group, K panel): nq =
+// G KP / 64 panels through ONE prefetch pipeline, so the first panel of group g + 1 is on its way into registers while the
+// last panel of group g multiplies and nothing drains at a group boundary.  There the wave stores its accumulators as they
+// are and seeds them again from the next bias; the slab's x columns are read again per group (L2 hits, 32 KiB per wave).
+// A 64-row group runs on the same four row tiles with zero weights past row 64 and stores the ATL(64) half (tiles 0 and 1): one
+// instantiation, no second accumulator shape in the loop, at the price of idle MFMAs in the one group that can be 64 rows.
+__global__ __launch_bounds__(WG_THREADS, 2) void k_rect_linear_groups(const float *__restrict__ xin, int KP, GroupTab tab, long n_slabs) {
+  constexpr int MT = 4, NSUB = 8 / MT, SUB = MT * 128;
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  u32x4 *img = reinterpret_cast<u32x4 *>(lds);
+  const int lane = threadIdx.x & 63, wave = wave_id(), h = lane >> 5;
+  const int ppg = KP / (32 * NSUB), nq = tab.n * ppg;  // panels per group, panels of the stream
+  const long n_iter = (n_slabs + WAVES_PER_WG - 1) / WAVES_PER_WG;
+  for (long it = blockIdx.x; it < n_iter; it += gridDim.x) {  // uniform trip count: barriers inside
+    const long s_raw = it * WAVES_PER_WG + wave;
+    const bool live = s_raw < n_slabs;
+    const long slab = live ? s_raw : n_slabs - 1;
+    const f32x4 *xp = reinterpret_cast<const f32x4 *>(xin + slab * (long)KP * SLAB) + lane;
+    f32x16 acc[MT];
+    auto seed = [&](int g) {
+      const float *bg = pick(tab.b, g);
+      const int sp = pick(tab.sp, g);
+#pragma unroll
+      for (int t = 0; t < MT; ++t) {
+        const bool in = 32 * t < sp;  // (a 64-row group has no bias past row 64: tiles 2 and 3 start from 0 and stay there)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const float v = bg[(in ? 32 * t : 0) + (r & 3) + 8 * (r >> 2) + 4 * h];
+          acc[t][r] = in ? v : 0.f;
+        }
+      }
+    };
+    seed(0);
+    float w[PER_THREAD][8];
+    load_panel_rows(w, tab.W[0], KP, tab.sp[0], 0);
+    __syncthreads();  // the last panel of the iteration before is no longer being read
+    commit_panel<MT>(img, w, NSUB);
+    int g = 0, p = 0;
+    for (int q = 0; q < nq; ++q) {
+      float xa[16];
+      load_cols<false>(xp, nullptr, 0, p * NSUB, xa);
+      const bool more = q + 1 < nq, last = p + 1 == ppg;
+      const int gn = last ? g + 1 : g, pn = last ? 0 : p + 1;
+      if (more) load_panel_rows(w, pick(tab.W, gn), KP, pick(tab.sp, gn), pn);
+      __syncthreads();  // panel q is complete
+      const u32x4 *wl = img + lane;
+#pragma unroll
+      for (int sub = 0; sub < NSUB; ++sub) {
+        u32x4 x1[2], x2[2], x3[2];
+        split_acts<16>(xa, x1, x2, x3);
+        float xb[16];
+        if (sub + 1 < NSUB) load_cols<false>(xp, nullptr, 0, p * NSUB + sub + 1, xb);
+        split_gemm<MT, 2>(wl + sub * 3 * SUB, x1, x2, x3, acc, [](int) {});
+        if (sub + 1 < NSUB) {
+#pragma unroll
+          for (int c = 0; c < 16; ++c) xa[c] = xb[c];
+        }
+      }
+      if (more) {
+        __syncthreads();  // one buffer: every wave has drained panel q
+        commit_panel<MT>(img, w, NSUB);
+      }
+      if (last) {  // group g is complete: its logits leave raw, the accumulators start over from the next bias
+        if (live) {
+          float *zg = pick(tab.img, g);
+          if (pick(tab.sp, g) == 128) {
+            float v[64];
+#pragma unroll
+            for (int R = 0; R < 64; ++R) v[R] = acc[R >> 4][R & 15];
+            atl_store<128>(zg, slab, lane, v);
+          } else {
+            float v[32];
+#pragma unroll
+            for (int R = 0; R < 32; ++R) v[R] = acc[R >> 4][R & 15];
+            atl_store<64>(zg, slab, lane, v);
+          }
+        }
+        if (more) seed(gn);
+      }
+      g = gn;
+      p = pn;
+    }
+  }
+}
+
+// backward: where sub-panel s of the K stream lies -- the group whose prefix of sp / 32 sub-panels contains it (the tangent
+// mode's n_first over a table) -- as that group's pack, dz image, image width and the sub-panel's place inside the group
+struct GroupSub {
+  const float *W, *img;
+  int sp, s;
+};
+__device__ __forceinline__ GroupSub group_sub(const GroupTab &tab, int s) {
+  GroupSub r{tab.W[0], tab.img[0], tab.sp[0], s};
+#pragma unroll
+  for (int k = 1; k < MAX_GROUPS; ++k)
+    if (s >= tab.first[k]) r = GroupSub{tab.W[k], tab.img[k], tab.sp[k], s - tab.first[k]};  // (workgroup-uniform)
+  return r;
+}
+
+// ... the fp32 weights of panel p of that stream, transposed: A[row][k] = W_g[k * ld + row], every k of a group valid
+template <int MT>
+__device__ __forceinline__ void load_panel_groups(float (&w)[PER_THREAD][8], const GroupTab &tab, int ld, int p, int nsub) {
+  constexpr int SUB = MT * 128, NSUB = 8 / MT;
+  const int r0 = threadIdx.x % SUB, ln = r0 & 63, j = (r0 >> 6) & 1, m0 = 32 * (r0 >> 7) + (ln & 31), kl = 16 * j + 4 * (ln >> 5);
+  const unsigned voff = (unsigned)(kl * ld + m0);
+#pragma unroll
+  for (int u = 0; u < PER_THREAD; ++u) {
+    const int sub = (u * WG_THREADS) / SUB, dm = 32 * (((u * WG_THREADS) % SUB) >> 7);
+    if (sub < nsub) {  // (workgroup-uniform)
+      const GroupSub gs = group_sub(tab, p * NSUB + sub);
+#pragma unroll
+      for (int c = 0; c < 8; ++c) w[u][c] = (gs.W + ((32 * gs.s + feat_base(c)) * ld + dm))[voff];
+    } else {
+#pragma unroll
+      for (int c = 0; c < 8; ++c) w[u][c] = 0.f;
+    }
+  }
+}
+
+__device__ __forceinline__ void load_cols_groups(const GroupTab &tab, long slab, int lane, int s, float (&x)[16]) {
+  const GroupSub gs = group_sub(tab, s);
+  load_cols<false>(reinterpret_cast<const f32x4 *>(gs.img + slab * (long)gs.sp * SLAB) + lane, nullptr, 0, gs.s, x);
+}
+
+// dz_prev = relu' . LNbwd(sum_g W'_g^T dz_g): the backward mode of k_panel_rect with its K stream running over the groups
+// (n_sub = sum_g sp_g / 32 sub-panels, at most 16; a panel may hold sub-panels of two groups).  The sum over the groups is the
+// GEMM's own K loop and the LayerNorm backward runs once, on the total.
+template <int MT>
+__global__ __launch_bounds__(WG_THREADS, MT == 8 ? 1 : 2) void k_rect_bwd_groups(
+    GroupTab tab, int n_sub, float *__restrict__ xout, const float *__restrict__ xprev, const uint32_t *__restrict__ mask_prev,
+    const float *__restrict__ rstd_prev, long n_slabs) {
+  constexpr int H = 32 * MT, NSUB = 8 / MT, NBUF = MT == 8 ? 2 : 1, SUB = MT * 128, BUF = 3 * PANEL_FRAGS;
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  u32x4 *img = reinterpret_cast<u32x4 *>(lds);
+  const int lane = threadIdx.x & 63, wave = wave_id(), i = lane & 31;
+  const int n_panels = (n_sub + NSUB - 1) / NSUB;
+  const long n_iter = (n_slabs + WAVES_PER_WG - 1) / WAVES_PER_WG;
+  for (long it = blockIdx.x; it < n_iter; it += gridDim.x) {  // uniform trip count: barriers inside
+    const long s_raw = it * WAVES_PER_WG + wave;
+    const bool live = s_raw < n_slabs;
+    const long slab = live ? s_raw : n_slabs - 1;
+    f32x16 acc[MT];
+#pragma unroll
+    for (int t = 0; t < MT; ++t)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
+    float w[PER_THREAD][8];
+    int nsub_p = n_sub < NSUB ? n_sub : NSUB;
+    load_panel_groups<MT>(w, tab, H, 0, nsub_p);
+    __syncthreads();  // the last panel of the iteration before is no longer being read
+    commit_panel<MT>(img, w, nsub_p);
+    for (int p = 0; p < n_panels; ++p) {
+      float xa[16];
+      load_cols_groups(tab, slab, lane, p * NSUB, xa);
+      const bool more = p + 1 < n_panels;
+      const int rest = n_sub - (p + 1) * NSUB, nsub_next = rest < NSUB ? rest : NSUB;
+      if (more) load_panel_groups<MT>(w, tab, H, p + 1, nsub_next);
+      __syncthreads();  // panel p is complete (and, with two buffers, panel p - 1 is no longer being read)
+      const u32x4 *wl = img + (p % NBUF) * BUF + lane;
+#pragma unroll
+      for (int sub = 0; sub < NSUB; ++sub)
+        if (sub < nsub_p) {
+          u32x4 x1[2], x2[2], x3[2];
+          split_acts<16>(xa, x1, x2, x3);
+          float xb[16];
+          if (sub + 1 < nsub_p) load_cols_groups(tab, slab, lane, p * NSUB + sub + 1, xb);
+          split_gemm<MT, 2>(wl + sub * 3 * SUB, x1, x2, x3, acc, [](int) {});
+          if (sub + 1 < nsub_p) {
+#pragma unroll
+            for (int c = 0; c < 16; ++c) xa[c] = xb[c];
+          }
+        }
+      if (more) {
+        if (NBUF == 1) __syncthreads();  // one buffer: every wave has drained panel p
+        commit_panel<MT>(img + ((p + 1) % NBUF) * BUF, w, nsub_next);
+      }
+      nsub_p = nsub_next;
+    }
+    if (!live) continue;
+    constexpr int NR = H / 2;
+    float dx[NR], xh[NR], out[NR];
+#pragma unroll
+    for (int R = 0; R < NR; ++R) dx[R] = acc[R >> 4][R & 15];
+    atl_load<H>(per_iteration(xprev), slab, lane, xh);
+    ln_bwd_relu_regs<H>(dx, xh, per_iteration(mask_prev), per_iteration(rstd_prev)[slab * SLAB + i], lane, slab, out);
+    atl_store<H>(per_iteration(xout), slab, lane, out);
+  }
+}
+
+template <int MT>
+void launch_bwd_groups(const GroupTab &tab, int n_sub, float *xout, const float *xprev, const uint32_t *mask_prev,
+                       const float *rstd_prev, long n_slabs, hipStream_t s) {
+  constexpr int NBUF = MT == 8 ? 2 : 1, WG_PER_CU = MT == 8 ? 1 : 2;
+  const size_t shm = (size_t)NBUF * 3 * PANEL_FRAGS * sizeof(u32x4);
+  allow_big_lds(k_rect_bwd_groups<MT>, shm);
+  hipLaunchKernelGGL((k_rect_bwd_groups<MT>), dim3(persistent_grid(n_slabs, WG_PER_CU)), dim3(WG_THREADS), shm, s, tab, n_sub, xout,
+                     xprev, mask_prev, rstd_prev, n_slabs);
+}
+
+// the host arrays of a grouped head as the kernels' table; false: not 1..4 groups of 64 / 128 rows.  Unused entries repeat
+// group 0 and start past any stream, so the selects never take them.
+bool group_tab(GroupTab &tab, int n_groups, const int *sp, const float *const *Wp, const float *const *bp, float *const *img) {
+  if (n_groups < 1 || n_groups > MAX_GROUPS || !sp || !Wp || !img) return false;
+  int first = 0;
+  for (int g = 0; g < MAX_GROUPS; ++g) {
+    const int k = g < n_groups ? g : 0;
+    if (sp[k] != 64 && sp[k] != 128) return false;
+    tab.W[g] = Wp[k];
+    tab.b[g] = bp ? bp[k] : nullptr;
+    tab.img[g] = img[k];
+    tab.sp[g] = sp[k];
+    tab.first[g] = g < n_groups ? first : 1 << 20;
+    first += sp[k] / 32;
+  }
+  tab.n = n_groups;
+  return true;
+}
 }  // namespace
 
 extern "C" int harl_mlp_rect_fwd(const float *xin, long M, int KP, const float *Wp, int D, const float *bp, int HO, float *xout,
@@ -330,4 +593,34 @@ extern "C" int harl_mlp_rect_tangent(const float *xin_dot, const float *xin, lon
   if (HO == 64) RECT(2); else if (HO == 128) RECT(4); else RECT(8);
 #undef RECT
   return check_launch("harl_mlp_rect_tangent");
+}
+
+extern "C" int harl_mlp_rect_linear_groups(const float *xin, long M, int KP, int n_groups, const int *sp, const float *const *Wp,
+                                           const float *const *bp, float *const *z, void *stream) {
+  if (M <= 0) return 0;
+  GroupTab tab;
+  if (!width_ok(KP) || !bp || !group_tab(tab, n_groups, sp, Wp, bp, z))
+    return bad("harl_mlp_rect_linear_groups: 1..4 groups of 64 / 128 rows on a head input of 64, 128 or 256 columns");
+  const long n_slabs = n_slabs_of(M);
+  const size_t shm = (size_t)3 * PANEL_FRAGS * sizeof(u32x4);
+  allow_big_lds(k_rect_linear_groups, shm);
+  hipLaunchKernelGGL(k_rect_linear_groups, dim3(persistent_grid(n_slabs, 2)), dim3(WG_THREADS), shm, (hipStream_t)stream, xin, KP, tab,
+                     n_slabs);
+  return check_launch("harl_mlp_rect_linear_groups");
+}
+
+extern "C" int harl_mlp_rect_bwd_groups(const float *const *dz, int n_groups, const int *sp, const float *const *Wp,
+                                        const float *xprev, const uint32_t *relu_mask_prev, const float *rstd_prev, long M, int HI,
+                                        float *dz_prev, void *stream) {
+  if (M <= 0) return 0;
+  GroupTab tab;
+  if (!width_ok(HI) || !group_tab(tab, n_groups, sp, Wp, nullptr, const_cast<float *const *>(dz)))
+    return bad("harl_mlp_rect_bwd_groups: 1..4 groups of 64 / 128 rows into a head input of 64, 128 or 256 columns");
+  int n_sub = 0;
+  for (int g = 0; g < n_groups; ++g) n_sub += sp[g] / 32;
+  const long n_slabs = n_slabs_of(M);
+#define RECT(MTv) launch_bwd_groups<MTv>(tab, n_sub, dz_prev, xprev, relu_mask_prev, rstd_prev, n_slabs, (hipStream_t)stream)
+  if (HI == 64) RECT(2); else if (HI == 128) RECT(4); else RECT(8);
+#undef RECT
+  return check_launch("harl_mlp_rect_bwd_groups");
 }

@@ -39,6 +39,8 @@ class HATRPO(OnPolicyBase):
         super().__init__(args, obs_space, act_space, device)  # (HARL_TRPO_CAT_WIDE=1: n > 512, 256-wide and non-ReLU are refused there)
         if self.actor.cat_wide and self.actor.recurrent and self.actor.gru_wide:
             raise NotImplementedError(CAT_WIDE_REFUSALS["hatrpo_gru_wide"])
+        if self.actor.cat_wide and self.actor.panel:  # (HARL_CAT_WIDE_256=1 opens these heads to the other algorithms: no tangent here)
+            raise NotImplementedError(CAT_WIDE_REFUSALS["panel"])
         self.kl_threshold = args["kl_threshold"]
         self.ls_step = args["ls_step"]
         self.accept_ratio = args["accept_ratio"]

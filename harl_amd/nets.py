@@ -23,7 +23,7 @@ import torch.nn as nn
 from . import _lib
 from . import graphs as _graphs
 from ._lib import DHEAD_LD, PS_STRIDE, SLAB, call, ptr, stream
-from .configs import (CAT_WIDE_REFUSALS, GAUSS_WIDE_REFUSALS, bwd_k64, bwd_streams, gauss_wide_enabled, gauss_wide_reason, gru_dw6,
+from .configs import (GAUSS_WIDE_REFUSALS, bwd_k64, bwd_streams, cat_wide_reason, gauss_wide_enabled, gauss_wide_reason, gru_dw6,
                       is_mixed_256, mixed_256_enabled, mixed_256_reason, trunk_dw_stream)
 
 SUPPORTED_WIDTHS = (64, 128, 256)
@@ -1074,9 +1074,22 @@ class _FlatNet(nn.Module):
 
     # ---- grouped heads (MultiDiscrete: csrc/multihead.hip, Categorical of 65..512 actions: csrc/cathead.hip): logits of every
     # group from the head input; backward of the groups
+    def _group_arrays(self):
+        """(n_groups, sp[], pack pointers, bias pointers, image pointers): the host arrays of the grouped launches of csrc/rect.hip."""
+        G = len(self._md_sp)
+        arr = lambda ts: (C.c_void_p * G)(*[t.data_ptr() for t in ts])  # noqa: E731
+        return (G, (C.c_int * G)(*self._md_sp), arr([w for w, _ in self._head_packs]), arr([b for _, b in self._head_packs]),
+                arr(self.md_z))
+
     def md_logits(self, M: int) -> None:
+        """The logits image of every group from the head input.  Trunks that hold a 256-wide layer (HARL_CAT_WIDE_256=1): ONE
+        launch over all groups, whatever the width of the last layer; every other trunk: harl_mlp_linear per group."""
         fx, _, _, fh = self.feat()
         s = stream()
+        if self.panel:
+            G, sps, Ws, bs, zs = self._group_arrays()
+            call("harl_mlp_rect_linear_groups", ptr(fx), M, fh, G, sps, Ws, bs, zs, s, tag="md_linear_groups")
+            return
         for (Wp, bp), z, sp in zip(self._head_packs, self.md_z, self._md_sp):
             call("harl_mlp_linear", ptr(fx), M, fh, sp, ptr(Wp), ptr(bp), ptr(z), s, tag="md_linear")
 
@@ -1113,10 +1126,19 @@ class _FlatNet(nn.Module):
 
     def md_backward(self, M: int) -> None:
         """d(loss)/d(logits) images (self.md_z, written by harl_md_head_loss / harl_cat_head_loss) -> the groups' weight-gradient partials and
-        d(loss)/d(head input) in self.dz[0]: the layer kernels of a hidden Linear (sum over the groups)."""
+        d(loss)/d(head input) in self.dz[0]: the layer kernels of a hidden Linear (sum over the groups).  Trunks that hold a
+        256-wide layer (HARL_CAT_WIDE_256=1): the weight gradients per group as everywhere, then ONE backward over all groups with
+        the sum inside its K loop (self.dz[0]: _backward_panel takes over from there)."""
         fx, fmask, frstd, fh = self.feat()
         s = stream()
         nh = len(self._md_sp)  # (the groups are the last nh table entries)
+        if self.panel:
+            for g, (dzg, sp) in enumerate(zip(self.md_z, self._md_sp)):
+                self._dw_atl(dzg, sp, fx, fh, M, g - nh, s, "dw_head")
+            G, sps, Ws, _, zs = self._group_arrays()
+            call("harl_mlp_rect_bwd_groups", zs, G, sps, Ws, ptr(fx), ptr(fmask), ptr(frstd), M, fh, ptr(self.dz[0]), s,
+                 tag="bwd_dx_groups")
+            return
         for g, ((Wp, _), dzg, sp) in enumerate(zip(self._head_packs, self.md_z, self._md_sp)):
             self._dw_atl(dzg, sp, fx, fh, M, g - nh, s, "dw_head")
             call("harl_mlp_bwd_dx", ptr(dzg), ptr(fx), ptr(fmask), ptr(frstd), M, sp, fh, ptr(Wp),
@@ -1204,12 +1226,9 @@ class StochasticPolicy(_FlatNet):
         rows [128 g, min(128 (g + 1), n)), one table entry, folded pack, logits image and weight-gradient partial block each;
         the last group is an ATL(64) image when it holds <= 64 rows."""
         n = self.act_dim
-        if n > 512:
-            raise NotImplementedError(CAT_WIDE_REFUSALS["n"])
-        if self.panel:
-            raise NotImplementedError(CAT_WIDE_REFUSALS["panel"])
-        if self.act_id:
-            raise NotImplementedError(CAT_WIDE_REFUSALS["act"])
+        why = cat_wide_reason(n, self.hidden_sizes, self.activation_func)  # (HARL_CAT_WIDE_256=1 lifts "panel": md_logits / md_backward)
+        if why is not None:
+            raise NotImplementedError(why)
         self.cat_wide = True
         self._cat_rows = [min(128, n - lo) for lo in range(0, n, 128)]
         self._md_sp = [64 if r <= 64 else 128 for r in self._cat_rows]

@@ -250,6 +250,18 @@ def _tangent_rect(a: Sequence) -> float:
     return a[2] * (4.0 * a[3] * (2 if a[0] else 1) + _act(a[4]) + 4.0 * a[4])
 
 
+def _linear_groups(a: Sequence) -> float:
+    # (xin, M, KP, n_groups, sp, Wp, bp, z, stream), tag md_linear_groups: the head input once (the re-reads per group are L2
+    # hits, traffic but not algorithm), every logits image out
+    return a[1] * (4.0 * a[2] + 4.0 * sum(a[4][g] for g in range(a[3])))
+
+
+def _bwd_groups(a: Sequence) -> float:
+    # (dz, n_groups, sp, Wp, xprev, relu_mask_prev, rstd_prev, M, HI, dz_prev, stream), tag bwd_dx_groups: every dz image once,
+    # the x_hat / mask / rstd of the head input, dz_prev out -- no per-group partial result crosses HBM
+    return a[7] * (4.0 * sum(a[2][g] for g in range(a[1])) + _act(a[8]) + 4.0 * a[8])
+
+
 def _gae(a: Sequence) -> float:
     # rewards, value_preds (T+1), masks (T+1), bad_masks (T+1) in; returns (T+1), advantages out
     T, n = a[8], a[9]
@@ -291,6 +303,8 @@ ALGORITHMIC_BYTES: Dict[str, Callable[[Sequence], float]] = {
     "harl_mlp_rect_fwd": _panel_fwd,  # (csrc/rect.hip: the same arguments, the same bytes per row)
     "harl_mlp_rect_bwd": _panel_bwd,
     "harl_mlp_rect_tangent": _tangent_rect,
+    "harl_mlp_rect_linear_groups": _linear_groups,
+    "harl_mlp_rect_bwd_groups": _bwd_groups,
     "harl_cat_head_logp": _cat_head_logp,
     "harl_cat_head_loss": _cat_head_loss,
     "harl_cat_head_fvp": _cat_head_fvp,
@@ -419,6 +433,8 @@ ALGORITHMIC_FLOPS: Dict[str, Callable[[Sequence], float]] = {
     "harl_mlp_rect_fwd": lambda a: 2.0 * a[1] * a[4] * a[6],
     "harl_mlp_rect_bwd": lambda a: 2.0 * a[4] * a[5] * a[6],
     "harl_mlp_rect_tangent": lambda a: 2.0 * (2 if a[0] else 1) * a[2] * a[7] * a[4],  # one GEMM for a first layer, two for a hidden one
+    "harl_mlp_rect_linear_groups": lambda a: 2.0 * a[1] * a[2] * sum(a[4][g] for g in range(a[3])),
+    "harl_mlp_rect_bwd_groups": lambda a: 2.0 * a[7] * a[8] * sum(a[2][g] for g in range(a[1])),
     "harl_gru_fwd": _f_gru_fwd,
     "harl_gru_bwd": _f_gru_bwd,
     "harl_actor_head_loss": lambda a: _f_head(a[3], a[4], a[11], True) - (2.0 * a[3] * a[11] * a[4] if not a[30] else 0.0),

@@ -222,6 +222,22 @@ int harl_mlp_rect_bwd(const float *dz, const float *xprev, const uint32_t *relu_
 int harl_mlp_rect_tangent(const float *xin_dot, const float *xin, long M, int KP, int HO, const float *Wp, const float *Wdp,
                           int D, const float *bdp, const float *xprimal, const uint32_t *mask_in, const float *rstd_in,
                           float *xout_dot, void *stream);
+/* A grouped head on a trunk that holds a 256-wide layer (opt-in HARL_CAT_WIDE_256=1): the Categorical(hidden, n) of a
+ * Discrete(n) space with 65 <= n <= 512 (harl/models/base/act.py:24-43 with distributions.py:37-55), cut into n_groups <= 4
+ * groups of sp_g = 64 / 128 rows as described at harl_cat_head_logp below.  sp, Wp, bp, z, dz: HOST arrays of n_groups entries
+ * (device pointers: the folded packs [sp_g][width], the biases [sp_g], the ATL(sp_g) images); the kernels get them by value.
+ *   harl_mlp_rect_linear_groups: z_g = Wp_g xin + bp_g for every group in ONE launch, raw (the role of n_groups
+ *     harl_mlp_linear), xin = ATL(KP) image, KP = 64 / 128 / 256.  The weight stream is one sequence of panels over (group, K
+ *     panel); a 64-row group runs on the four row tiles of a 128-row one with zero weights past row 64 and stores ATL(64).
+ *   harl_mlp_rect_bwd_groups: dz_prev = relu' . LNbwd(sum_g Wp_g^T dz_g) in ONE launch, HI = 64 / 128 / 256 (the role of
+ *     n_groups harl_mlp_bwd_dx and the sums between them): harl_mlp_rect_bwd with its K stream running over the groups, the
+ *     LayerNorm backward once on the total.  Rows past M of the last slab: dz_prev is 0 where every dz_g is.
+ * Other shapes: -2 and an error text.  Weight gradients: harl_mlp_dw_partials(a_kind = 0, HO = sp_g) per group. */
+int harl_mlp_rect_linear_groups(const float *xin, long M, int KP, int n_groups, const int *sp, const float *const *Wp,
+                                const float *const *bp, float *const *z, void *stream);
+int harl_mlp_rect_bwd_groups(const float *const *dz, int n_groups, const int *sp, const float *const *Wp, const float *xprev,
+                             const uint32_t *relu_mask_prev, const float *rstd_prev, long M, int HI, float *dz_prev,
+                             void *stream);
 /* the same two layers FROM the x0n ATL(32 | 64) image of harl_mlp_x0n_wide (D <= 64; identity row order; the image is
  * built once per buffer): no gather, no input-LayerNorm work per call */
 int harl_mlp_fwd_fused2x(const float *x0n, long M, const float *W1p, int D, const float *b1p, const float *W2p,

@@ -138,6 +138,30 @@ def main():
         ("h17_tangent_rect_256to256", rect(256, 256), GF(2 * 2.0 * B2 * 256 * 256)),
         ("h17_tangent_panel_256to256", lambda: call("harl_mlp_panel_tangent", ptr(yb), ptr(ya), B2, 256, ptr(Wr), ptr(Wrd), 256, ptr(br), ptr(yc), ptr(mask4_), ptr(rstd2_), ptr(yo), s), GF(2 * 2.0 * B2 * 256 * 256)),
     ]
+    # ---- a Categorical head of 512 actions (four groups of 128 rows) on a 128-wide head input, the same rows: the grouped
+    # launches of csrc/rect.hip (HARL_CAT_WIDE_256=1) next to the launches they stand in for on trunks that hold a 256-wide layer
+    import ctypes as C
+    zg = [rn(mp2 * H) for _ in range(4)]
+    Wg, bg = [rn(H * H) * 0.1 for _ in range(4)], [rn(H) * 0.1 for _ in range(4)]
+    arr = lambda ts: (C.c_void_p * 4)(*[t.data_ptr() for t in ts])  # noqa: E731
+    sp4, zs4, Ws4, bs4 = (C.c_int * 4)(*[H] * 4), arr(zg), arr(Wg), arr(bg)
+
+    def four_linear():
+        for g_ in range(4):
+            call("harl_mlp_linear", ptr(xa), B2, H, H, ptr(Wg[g_]), ptr(bg[g_]), ptr(zg[g_]), s)
+
+    def four_bwd_dx():
+        for g_ in range(4):
+            call("harl_mlp_bwd_dx", ptr(zg[g_]), ptr(xb), ptr(mask2_), ptr(rstd2_), B2, H, H, ptr(Wg[g_]), ptr(xo if g_ == 0 else xc), None, 0, None, 0, s)
+            if g_:
+                xo.add_(xc)
+
+    jobs += [
+        ("h17_cat512_linear_groups", lambda: call("harl_mlp_rect_linear_groups", ptr(xa), B2, H, 4, sp4, Ws4, bs4, zs4, s), GF(4 * fl2)),
+        ("h17_cat512_linear_x4", four_linear, GF(4 * fl2)),
+        ("h17_cat512_bwd_groups", lambda: call("harl_mlp_rect_bwd_groups", zs4, 4, sp4, Ws4, ptr(xb), ptr(mask2_), ptr(rstd2_), B2, H, ptr(xo), s), GF(4 * fl2)),
+        ("h17_cat512_bwd_dx_x4_add", four_bwd_dx, GF(4 * fl2)),
+    ]
     print(f"B={B}  H={H}  reps={args.reps}  lib={_lib.LIB_PATH}")
     for name, fn, (unit, work) in jobs:
         if args.filters and not any(f in name for f in args.filters):
