@@ -113,6 +113,7 @@ SIGNATURES = {
     "harl_mlp_rect_tangent": [_vp, _vp, _l, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp],
     "harl_mlp_rect_linear_groups": [_vp, _l, _i, _i, _vp, _vp, _vp, _vp, _vp],
     "harl_mlp_rect_bwd_groups": [_vp, _i, _vp, _vp, _vp, _vp, _vp, _l, _i, _vp, _vp],
+    "harl_mlp_rect_tangent_groups": [_vp, _vp, _l, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp],
     "harl_head_dw_rows256": [_vp, _l, _i, _vp, _vp, _i, _vp],
     "harl_mlp_panel_tangent": [_vp, _vp, _l, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp],
     "harl_reduce_scalars": [_vp, _i, _vp, _vp],

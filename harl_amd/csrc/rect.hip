@@ -419,6 +419,108 @@ __global__ __launch_bounds__(WG_THREADS, 2) void k_rect_linear_groups(const floa
   }
 }
 
+// ---- the tangent of the grouped logits (HATRPO's Fisher-vector product on these heads, opt-in HARL_TRPO_CAT_WIDE_256=1):
+//   z_dot_g = W'_g_dot x_hat + b'_g_dot + W'_g x_dot      for every group g, raw, ONE ATL(sp_g) image per group
+// k_rect_linear_groups crossed with the two-operand stream of k_panel_rect<MT, 2>.  The table of a group holds both matrices:
+// operand 0 is (W'_g_dot, x_hat), operand 1 is (W'_g, x_dot).
+struct TangentTab {
+  const float *W[MAX_GROUPS];   // folded pack [sp][ld]
+  const float *Wd[MAX_GROUPS];  // its tangent [sp][ld]
+  const float *bd[MAX_GROUPS];  // the bias' tangent [sp]
+  float *zd[MAX_GROUPS];        // the ATL(sp) tangent image (out)
+  int sp[MAX_GROUPS];           // 64 / 128
+  int n;
+};
+
+// The weight stream runs over (group, operand, K panel): nq = 2 G KP / 64 panels of 64 columns through the ONE register
+// prefetch and the one 48 KiB buffer of the forward.  Nothing drains between the two operands of a group or between groups:
+// while the last panel of (g, W') multiplies, the first panel of (g + 1, W'_dot) is in registers.  Which matrix a panel reads
+// and which image the slab's columns come from are functions of the stream position alone, so workgroup-uniform: the matrix is
+// a scalar select in front of load_panel_rows, the image a scalar select of the base in front of ONE lane address -- no second
+// lane pointer lives across the loop.  Both operands add into the same accumulators, seeded from b'_g_dot; after operand 1 the
+// wave stores them raw and seeds them from the next group's bias.  64-row groups and dead waves as in the forward.
+__global__ __launch_bounds__(WG_THREADS, 2) void k_rect_tangent_groups(const float *__restrict__ xin, const float *__restrict__ xin_dot,
+                                                                      int KP, TangentTab tab, long n_slabs) {
+  constexpr int MT = 4, NSUB = 8 / MT, SUB = MT * 128;
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  u32x4 *img = reinterpret_cast<u32x4 *>(lds);
+  const int lane = threadIdx.x & 63, wave = wave_id(), h = lane >> 5;
+  const int ppo = KP / (32 * NSUB), nq = tab.n * 2 * ppo;  // panels per operand, panels of the stream
+  const long n_iter = (n_slabs + WAVES_PER_WG - 1) / WAVES_PER_WG;
+  for (long it = blockIdx.x; it < n_iter; it += gridDim.x) {  // uniform trip count: barriers inside
+    const long s_raw = it * WAVES_PER_WG + wave;
+    const bool live = s_raw < n_slabs;
+    const long slab = live ? s_raw : n_slabs - 1;
+    const long xoff = slab * (long)KP * SLAB + 4 * lane;  // this lane's place in either image of the slab
+    f32x16 acc[MT];
+    auto seed = [&](int g) {
+      const float *bg = pick(tab.bd, g);
+      const int sp = pick(tab.sp, g);
+#pragma unroll
+      for (int t = 0; t < MT; ++t) {
+        const bool in = 32 * t < sp;  // (a 64-row group has no bias past row 64: tiles 2 and 3 start from 0 and stay there)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const float v = bg[(in ? 32 * t : 0) + (r & 3) + 8 * (r >> 2) + 4 * h];
+          acc[t][r] = in ? v : 0.f;
+        }
+      }
+    };
+    seed(0);
+    float w[PER_THREAD][8];
+    load_panel_rows(w, tab.Wd[0], KP, tab.sp[0], 0);
+    __syncthreads();  // the last panel of the iteration before is no longer being read
+    commit_panel<MT>(img, w, NSUB);
+    int g = 0, o = 0, p = 0;
+    for (int q = 0; q < nq; ++q) {
+      const f32x4 *xp = reinterpret_cast<const f32x4 *>((o ? xin_dot : xin) + xoff);  // (workgroup-uniform base)
+      float xa[16];
+      load_cols<false>(xp, nullptr, 0, p * NSUB, xa);
+      const bool more = q + 1 < nq, last = p + 1 == ppo, done = last && o == 1;
+      const int pn = last ? 0 : p + 1, on = last ? o ^ 1 : o, gn = done ? g + 1 : g;
+      if (more) load_panel_rows(w, on ? pick(tab.W, gn) : pick(tab.Wd, gn), KP, pick(tab.sp, gn), pn);
+      __syncthreads();  // panel q is complete
+      const u32x4 *wl = img + lane;
+#pragma unroll
+      for (int sub = 0; sub < NSUB; ++sub) {
+        u32x4 x1[2], x2[2], x3[2];
+        split_acts<16>(xa, x1, x2, x3);
+        float xb[16];
+        if (sub + 1 < NSUB) load_cols<false>(xp, nullptr, 0, p * NSUB + sub + 1, xb);
+        split_gemm<MT, 2>(wl + sub * 3 * SUB, x1, x2, x3, acc, [](int) {});
+        if (sub + 1 < NSUB) {
+#pragma unroll
+          for (int c = 0; c < 16; ++c) xa[c] = xb[c];
+        }
+      }
+      if (more) {
+        __syncthreads();  // one buffer: every wave has drained panel q
+        commit_panel<MT>(img, w, NSUB);
+      }
+      if (done) {  // both operands of group g are in: its tangent leaves raw, the accumulators start over from the next bias
+        if (live) {
+          float *zg = pick(tab.zd, g);
+          if (pick(tab.sp, g) == 128) {
+            float v[64];
+#pragma unroll
+            for (int R = 0; R < 64; ++R) v[R] = acc[R >> 4][R & 15];
+            atl_store<128>(zg, slab, lane, v);
+          } else {
+            float v[32];
+#pragma unroll
+            for (int R = 0; R < 32; ++R) v[R] = acc[R >> 4][R & 15];
+            atl_store<64>(zg, slab, lane, v);
+          }
+        }
+        if (more) seed(gn);
+      }
+      g = gn;
+      o = on;
+      p = pn;
+    }
+  }
+}
+
 // backward: where sub-panel s of the K stream lies -- the group whose prefix of sp / 32 sub-panels contains it (the tangent
 // mode's n_first over a table) -- as that group's pack, dz image, image width and the sub-panel's place inside the group
 struct GroupSub {
@@ -607,6 +709,32 @@ extern "C" int harl_mlp_rect_linear_groups(const float *xin, long M, int KP, int
   hipLaunchKernelGGL(k_rect_linear_groups, dim3(persistent_grid(n_slabs, 2)), dim3(WG_THREADS), shm, (hipStream_t)stream, xin, KP, tab,
                      n_slabs);
   return check_launch("harl_mlp_rect_linear_groups");
+}
+
+extern "C" int harl_mlp_rect_tangent_groups(const float *xin_dot, const float *xin, long M, int KP, int n_groups, const int *sp,
+                                            const float *const *Wp, const float *const *Wdp, const float *const *bdp,
+                                            float *const *zd, void *stream) {
+  if (M <= 0) return 0;
+  bool ok = xin_dot && xin && width_ok(KP) && n_groups >= 1 && n_groups <= MAX_GROUPS && sp && Wp && Wdp && bdp && zd;
+  for (int g = 0; ok && g < n_groups; ++g) ok = (sp[g] == 64 || sp[g] == 128) && Wp[g] && Wdp[g] && bdp[g] && zd[g];
+  if (!ok)
+    return bad("harl_mlp_rect_tangent_groups: 1..4 groups of 64 / 128 rows on a head input of 64, 128 or 256 columns, every pointer given");
+  TangentTab tab;
+  for (int g = 0; g < MAX_GROUPS; ++g) {  // (unused entries repeat group 0: the stream never reaches them)
+    const int k = g < n_groups ? g : 0;
+    tab.W[g] = Wp[k];
+    tab.Wd[g] = Wdp[k];
+    tab.bd[g] = bdp[k];
+    tab.zd[g] = zd[k];
+    tab.sp[g] = sp[k];
+  }
+  tab.n = n_groups;
+  const long n_slabs = n_slabs_of(M);
+  const size_t shm = (size_t)3 * PANEL_FRAGS * sizeof(u32x4);
+  allow_big_lds(k_rect_tangent_groups, shm);
+  hipLaunchKernelGGL(k_rect_tangent_groups, dim3(persistent_grid(n_slabs, 2)), dim3(WG_THREADS), shm, (hipStream_t)stream, xin, xin_dot,
+                     KP, tab, n_slabs);
+  return check_launch("harl_mlp_rect_tangent_groups");
 }
 
 extern "C" int harl_mlp_rect_bwd_groups(const float *const *dz, int n_groups, const int *sp, const float *const *Wp,

@@ -19,7 +19,7 @@ from . import _lib
 from ._lib import call, ptr, stream
 from .buffers import OnPolicyActorBuffer, consume_randperm, rng_sync
 from .configs import (CAT_WIDE_REFUSALS, GAUSS_WIDE_REFUSALS, MIXED_256_REFUSALS, gauss_wide_enabled, is_mixed_256,
-                      mixed_256_enabled, trpo_cat_wide_enabled, trpo_mixed_256_enabled)
+                      mixed_256_enabled, trpo_cat_wide_256_enabled, trpo_cat_wide_enabled, trpo_mixed_256_enabled)
 from .happo import OnPolicyBase
 from .nets import build_seq, consume_policy_init_rng, seq_compact
 from .valuenorm import _as_dev
@@ -39,7 +39,8 @@ class HATRPO(OnPolicyBase):
         super().__init__(args, obs_space, act_space, device)  # (HARL_TRPO_CAT_WIDE=1: n > 512, 256-wide and non-ReLU are refused there)
         if self.actor.cat_wide and self.actor.recurrent and self.actor.gru_wide:
             raise NotImplementedError(CAT_WIDE_REFUSALS["hatrpo_gru_wide"])
-        if self.actor.cat_wide and self.actor.panel:  # (HARL_CAT_WIDE_256=1 opens these heads to the other algorithms: no tangent here)
+        if self.actor.cat_wide and self.actor.panel and not trpo_cat_wide_256_enabled():
+            # (HARL_CAT_WIDE_256=1 opens these heads to the other algorithms; their logits' tangent, nets._cat_head_fvp, is opt-in)
             raise NotImplementedError(CAT_WIDE_REFUSALS["panel"])
         self.kl_threshold = args["kl_threshold"]
         self.ls_step = args["ls_step"]
@@ -101,8 +102,9 @@ class HATRPO(OnPolicyBase):
             self._tangent_ws = dict(rows=m, xd=[torch.empty(mp * h, **self.tpdv) for h in hs],
                                     # (zeros: a group's tangent pack keeps the zero rows past its last action, like the pack)
                                     pack_d=torch.zeros_like(net.pack_arena) if net.grouped else torch.empty_like(net.pack_arena))
-            if net.grouped:  # nets._cat_head_fvp: the two halves of every group's logits tangent
-                self._tangent_ws["cat_zd"] = [[torch.empty(mp * sp, **self.tpdv) for sp in net._md_sp] for _ in range(2)]
+            if net.grouped:  # nets._cat_head_fvp: the two halves of every group's logits tangent (panel trunks: ONE image, the sum)
+                self._tangent_ws["cat_zd"] = [[torch.empty(mp * sp, **self.tpdv) for sp in net._md_sp]
+                                              for _ in range(1 if net.panel else 2)]
                 self._tangent_ws["cat_zero_bias"] = torch.zeros(128, **self.tpdv)
             if net.recurrent:
                 H = hs[-1]

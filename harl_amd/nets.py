@@ -1111,11 +1111,23 @@ class _FlatNet(nn.Module):
         b'_g_dot as raw GEMMs into the caller's scratch images ``zd`` (two lists, one image per group; ``zero_bias``: 128
         zeros), then harl_cat_head_fvp, which leaves the log-softmax backward of q_dot in the logits images -- where
         backward_trunk (md_backward) reads d(loss)/d(logits) after a loss launch.  The groups are layer-table entries:
-        ``pack_d`` holds their W'_g_dot / b'_g_dot at the offsets of the folded packs (harl_fold_tangent_table)."""
+        ``pack_d`` holds their W'_g_dot / b'_g_dot at the offsets of the folded packs (harl_fold_tangent_table).  Trunks that
+        hold a 256-wide layer (HARL_TRPO_CAT_WIDE_256=1): both halves of every group in ONE launch, summed in its accumulators
+        into ONE list of images (harl_mlp_rect_tangent_groups, csrc/rect.hip)."""
         fx, _, _, fh = self.feat()
         s = stream()
         self.md_logits(M)
         G = len(self._md_sp)
+        if self.panel:
+            _, sps, Ws, _, _ = self._group_arrays()
+            arr = lambda ts: (C.c_void_p * G)(*[t.data_ptr() for t in ts])  # noqa: E731
+            slots = [(pw, pb, sp, k) for (pw, pb, _, k), sp in zip(self._pack_slots[-G:], self._md_sp)]
+            Wds, bds = arr([pack_d[pw:pw + sp * k] for pw, _, sp, k in slots]), arr([pack_d[pb:pb + sp] for _, pb, sp, _ in slots])
+            za = arr(zd[0])
+            call("harl_mlp_rect_tangent_groups", ptr(xLdot), ptr(fx), M, fh, G, sps, Ws, Wds, bds, za, s, tag="tangent_groups")
+            zs, _, _, n = self.cat_layout()
+            call("harl_cat_head_fvp", zs, za, None, G, sps, n, M, ptr(avail), m_valid, m_pad, s, tag="cat_head_fvp")
+            return
         for (Wp, _), (pw, pb, _, k), za, zb, sp in zip(self._head_packs, self._pack_slots[-G:], *zd, self._md_sp):
             call("harl_mlp_linear", ptr(xLdot), M, fh, sp, ptr(Wp), ptr(zero_bias), ptr(za), s, tag="md_linear")
             call("harl_mlp_linear", ptr(fx), M, fh, sp, ptr(pack_d[pw:pw + sp * k]), ptr(pack_d[pb:pb + sp]), ptr(zb), s,

@@ -262,6 +262,12 @@ def _bwd_groups(a: Sequence) -> float:
     return a[7] * (4.0 * sum(a[2][g] for g in range(a[1])) + _act(a[8]) + 4.0 * a[8])
 
 
+def _tangent_groups(a: Sequence) -> float:
+    # (xin_dot, xin, M, KP, n_groups, sp, Wp, Wdp, bdp, zd, stream), tag tangent_groups: the head input and its tangent once
+    # each (the re-reads per group are L2 hits), ONE tangent image per group out
+    return a[2] * (2 * 4.0 * a[3] + 4.0 * sum(a[5][g] for g in range(a[4])))
+
+
 def _gae(a: Sequence) -> float:
     # rewards, value_preds (T+1), masks (T+1), bad_masks (T+1) in; returns (T+1), advantages out
     T, n = a[8], a[9]
@@ -305,6 +311,7 @@ ALGORITHMIC_BYTES: Dict[str, Callable[[Sequence], float]] = {
     "harl_mlp_rect_tangent": _tangent_rect,
     "harl_mlp_rect_linear_groups": _linear_groups,
     "harl_mlp_rect_bwd_groups": _bwd_groups,
+    "harl_mlp_rect_tangent_groups": _tangent_groups,
     "harl_cat_head_logp": _cat_head_logp,
     "harl_cat_head_loss": _cat_head_loss,
     "harl_cat_head_fvp": _cat_head_fvp,
@@ -435,6 +442,7 @@ ALGORITHMIC_FLOPS: Dict[str, Callable[[Sequence], float]] = {
     "harl_mlp_rect_tangent": lambda a: 2.0 * (2 if a[0] else 1) * a[2] * a[7] * a[4],  # one GEMM for a first layer, two for a hidden one
     "harl_mlp_rect_linear_groups": lambda a: 2.0 * a[1] * a[2] * sum(a[4][g] for g in range(a[3])),
     "harl_mlp_rect_bwd_groups": lambda a: 2.0 * a[7] * a[8] * sum(a[2][g] for g in range(a[1])),
+    "harl_mlp_rect_tangent_groups": lambda a: 2.0 * 2 * a[2] * a[3] * sum(a[5][g] for g in range(a[4])),  # two GEMMs per group
     "harl_gru_fwd": _f_gru_fwd,
     "harl_gru_bwd": _f_gru_bwd,
     "harl_actor_head_loss": lambda a: _f_head(a[3], a[4], a[11], True) - (2.0 * a[3] * a[11] * a[4] if not a[30] else 0.0),

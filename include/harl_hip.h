@@ -238,6 +238,16 @@ int harl_mlp_rect_linear_groups(const float *xin, long M, int KP, int n_groups, 
 int harl_mlp_rect_bwd_groups(const float *const *dz, int n_groups, const int *sp, const float *const *Wp, const float *xprev,
                              const uint32_t *relu_mask_prev, const float *rstd_prev, long M, int HI, float *dz_prev,
                              void *stream);
+/* Forward-mode tangent of such a head's logits (HATRPO's Fisher-vector product on these heads; opt-in HARL_TRPO_CAT_WIDE_256=1
+ * next to HARL_TRPO_CAT_WIDE=1 and HARL_CAT_WIDE_256=1): zd_g = Wdp_g xin + bdp_g + Wp_g xin_dot for every group in ONE launch,
+ * raw, ONE ATL(sp_g) image per group (the role of 2 n_groups harl_mlp_linear and their two images per group; harl_cat_head_fvp
+ * then takes zd_b = NULL).  xin / xin_dot: the ATL(KP) images of the head input and of its tangent, KP = 64 / 128 / 256; Wp /
+ * Wdp: the folded packs [sp_g][KP] and their tangents, bdp: the biases' tangents [sp_g]; host arrays as above.  The weight
+ * stream is one sequence of panels over (group, operand, K panel) into the same accumulators.  Other shapes or a missing
+ * pointer: -2 and an error text. */
+int harl_mlp_rect_tangent_groups(const float *xin_dot, const float *xin, long M, int KP, int n_groups, const int *sp,
+                                 const float *const *Wp, const float *const *Wdp, const float *const *bdp, float *const *zd,
+                                 void *stream);
 /* the same two layers FROM the x0n ATL(32 | 64) image of harl_mlp_x0n_wide (D <= 64; identity row order; the image is
  * built once per buffer): no gather, no input-LayerNorm work per call */
 int harl_mlp_fwd_fused2x(const float *x0n, long M, const float *W1p, int D, const float *b1p, const float *W2p,

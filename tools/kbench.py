@@ -162,6 +162,23 @@ def main():
         ("h17_cat512_bwd_groups", lambda: call("harl_mlp_rect_bwd_groups", zs4, 4, sp4, Ws4, ptr(xb), ptr(mask2_), ptr(rstd2_), B2, H, ptr(xo), s), GF(4 * fl2)),
         ("h17_cat512_bwd_dx_x4_add", four_bwd_dx, GF(4 * fl2)),
     ]
+    # ---- the tangent of those logits (HARL_TRPO_CAT_WIDE_256=1): one launch into one image per group next to the 2 G
+    # harl_mlp_linear launches into two images per group of the 64 / 128-wide trunks; then the 256-wide head input, which has no
+    # other kernel
+    zg2, Wgd, zb128 = [torch.empty(mp2 * H, device=dev) for _ in range(4)], [rn(H * H) * 0.1 for _ in range(4)], torch.zeros(H, device=dev)
+    Wg256, Wgd256 = [rn(H * 256) * 0.06 for _ in range(4)], [rn(H * 256) * 0.06 for _ in range(4)]
+    Wds4, Ws256, Wds256 = arr(Wgd), arr(Wg256), arr(Wgd256)
+
+    def eight_linear():
+        for g_ in range(4):
+            call("harl_mlp_linear", ptr(xb), B2, H, H, ptr(Wg[g_]), ptr(zb128), ptr(zg[g_]), s)
+            call("harl_mlp_linear", ptr(xa), B2, H, H, ptr(Wgd[g_]), ptr(bg[g_]), ptr(zg2[g_]), s)
+
+    jobs += [
+        ("h17_cat512_tangent_groups", lambda: call("harl_mlp_rect_tangent_groups", ptr(xb), ptr(xa), B2, H, 4, sp4, Ws4, Wds4, bs4, zs4, s), GF(8 * fl2)),
+        ("h17_cat512_linear_x8", eight_linear, GF(8 * fl2)),
+        ("h17_cat512_tangent_groups_K256", lambda: call("harl_mlp_rect_tangent_groups", ptr(yb), ptr(ya), B2, 256, 4, sp4, Ws256, Wds256, bs4, zs4, s), GF(16 * fl2)),
+    ]
     print(f"B={B}  H={H}  reps={args.reps}  lib={_lib.LIB_PATH}")
     for name, fn, (unit, work) in jobs:
         if args.filters and not any(f in name for f in args.filters):
