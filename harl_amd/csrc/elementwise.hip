@@ -13,6 +13,7 @@
 #include <utility>
 
 #include "common.h"
+#include "act_funcs.h"
 #include "../../include/harl_hip.h"
 
 #include <cstdio>
@@ -681,27 +682,9 @@ __global__ __launch_bounds__(256) void k_reduce_partials(const float *__restrict
 //   harl_act_bwd    :  dz = da * act'(z), in place, with act' taken from the activation VALUE a = x_hat / rstd + mean
 //                      (tanh: 1 - a^2, sigmoid: a (1 - a), leaky_relu: a > 0 ? 1 : 0.01, selu: a > 0 ? scale : a + scale alpha)
 // where da is what the backward kernels produce when they are handed an all-ones ReLU mask (harl_mlp_bwd_dx, the loss
-// kernels' LayerNorm backward).  ACT ids: 1 leaky_relu, 2 tanh, 3 sigmoid, 4 selu.
+// kernels' LayerNorm backward).  ACT ids: 1 leaky_relu, 2 tanh, 3 sigmoid, 4 selu; act_value / act_slope_from_value: act_funcs.h.
+// harl_act_bwd also takes H = 256: the top layer of a non-ReLU trunk that holds a 256-wide layer (rect.hip's _act_ entry points).
 // =============================================================================================
-constexpr float SELU_SCALE = 1.0507009873554804934193349852946f, SELU_ALPHA = 1.6732632423543772848170429916717f;
-
-__device__ __forceinline__ float act_value(float z, int act) {
-  switch (act) {
-    case 1: return z > 0.f ? z : 0.01f * z;
-    case 2: return tanhf(z);
-    case 3: return 1.0f / (1.0f + expf(-z));
-    default: return z > 0.f ? SELU_SCALE * z : (SELU_SCALE * SELU_ALPHA) * (expf(z) - 1.0f);
-  }
-}
-__device__ __forceinline__ float act_slope_from_value(float a, int act) {
-  switch (act) {
-    case 1: return a > 0.f ? 1.0f : 0.01f;
-    case 2: return 1.0f - a * a;
-    case 3: return a * (1.0f - a);
-    default: return a > 0.f ? SELU_SCALE : a + SELU_SCALE * SELU_ALPHA;
-  }
-}
-
 template <int H>
 __global__ __launch_bounds__(WG_THREADS) void k_act_ln_fwd(const float *__restrict__ z, long n_slabs, int act,
                                                            float *__restrict__ xhat, float *__restrict__ mean_out,
@@ -838,8 +821,9 @@ extern "C" int harl_act_bwd(float *dz, const float *xhat, const float *mean, con
   const int grid = persistent_grid(n_slabs, 8);
   if (H == 128) hipLaunchKernelGGL(k_act_bwd<128>, dim3(grid), dim3(WG_THREADS), 0, (hipStream_t)stream, dz, xhat, mean, rstd, n_slabs, act);
   else if (H == 64) hipLaunchKernelGGL(k_act_bwd<64>, dim3(grid), dim3(WG_THREADS), 0, (hipStream_t)stream, dz, xhat, mean, rstd, n_slabs, act);
+  else if (H == 256) hipLaunchKernelGGL(k_act_bwd<256>, dim3(grid), dim3(WG_THREADS), 0, (hipStream_t)stream, dz, xhat, mean, rstd, n_slabs, act);
   else {
-    set_error("harl_act_bwd: width must be 64 or 128");
+    set_error("harl_act_bwd: width must be 64, 128 or 256");
     return -2;
   }
   return check_launch("harl_act_bwd");

@@ -29,11 +29,14 @@
 //   backward : dz_in = relu' . LNbwd(W'^T dz_out)               (HI, HO) over {64, 128, 256}^2
 //   tangent  : x_out_dot = LNjac(mask . (W'_dot x_in + b'_dot [+ W' x_in_dot]))   HATRPO's Fisher-vector product on these trunks
 //              (opt-in HARL_TRPO_MIXED_256=1): both products are ONE stream of sub-panels through the same prefetch pipeline
+//   ACT 1..4 : forward x_hat_out = norm(act(W' x_in + b')), backward dz_in = act'(a) . LNbwd(W'^T dz_out) for leaky_relu / tanh /
+//              sigmoid / selu (opt-in HARL_ACT_256=1): the same walk, another epilogue (see k_panel_rect)
 // The GEMM is split_mfma.h's exact three-term bf16 split, six products, fp32 accumulation; x_hat / ReLU mask words / rstd
 // leave in the layouts of the 64 / 128-wide layer kernels (fwd_epilogue.h) and of k_panel, so the head kernels,
 // harl_mlp_dw_partials and harl_mlp_bwd_dx read them unchanged.  Rows past M inside the last slab are computed like any
 // other: they never enter a sum because dz is 0 there (the loss kernels write it so, and LNbwd of a zero row is a zero row).
 #include "common.h"
+#include "act_funcs.h"
 #include "split_mfma.h"
 #include "../../include/harl_hip.h"
 
@@ -153,12 +156,23 @@ __device__ __forceinline__ T *per_iteration(T *p) {
 //   sub-panels (load_panel): the prefetch / commit pipeline below never learns where one operand ends, a panel may straddle the
 //   boundary (MT = 2, 64 -> 64: the whole K = 128 reduction is ONE panel), and there is no drain between the operands.  n_first
 //   counts the sub-panels that hold a valid column of Wp; the columns of x_in past them would meet zero weights and are skipped.
-template <int MT, int MODE>
+//
+// ACT 0 is ReLU, everything above.  ACT 1..4 (act_funcs.h: leaky_relu, tanh, sigmoid, selu; MODE 0 / 1, opt-in HARL_ACT_256=1) changes
+// the EPILOGUE only, where every accumulator of the slab already sits in this wave's registers -- the composed 64 / 128 route
+// (raw GEMM, harl_act_ln_fwd, harl_act_bwd) sends the pre-activation image through HBM for the same arithmetic:
+//   forward  : a = act(acc), x_hat = LayerNorm(a) in the two-pass form below; the record is x_hat, mean(a), rstd (mean_out,
+//              rstd_out) and there are no mask words -- the backward rebuilds a = x_hat / rstd + mean from it
+//   backward : dz_prev = act'(a) . LNbwd(W'^T dz) with act' taken from the value a (mean_prev, rstd_prev), multiplied into the
+//              LayerNorm backward's output in place: at MT = 8 nothing joins acc / x_hat / out, the three 128-register arrays
+//              live at the ReLU epilogue's peak.  A zero dz row still gives a zero row (0 times a finite slope).
+template <int MT, int MODE, int ACT = 0>
 __global__ __launch_bounds__(WG_THREADS, MT == 8 ? 1 : 2) void k_panel_rect(
     const float *__restrict__ xin, int KP, const float *__restrict__ Wp, int ldw, int kvalid, const float *__restrict__ bp,
     float *__restrict__ xout, uint32_t *__restrict__ mask_out, float *__restrict__ rstd_out, const float *__restrict__ xprev,
     const uint32_t *__restrict__ mask_prev, const float *__restrict__ rstd_prev, long n_slabs,
-    const float *__restrict__ xin2 = nullptr, const float *__restrict__ W2 = nullptr, int ld2 = 0, int n_first = 0) {
+    const float *__restrict__ xin2 = nullptr, const float *__restrict__ W2 = nullptr, int ld2 = 0, int n_first = 0,
+    float *__restrict__ mean_out = nullptr, const float *__restrict__ mean_prev = nullptr) {
+  static_assert(ACT >= 0 && ACT <= 4 && (ACT == 0 || MODE != 2), "the tangent has no activation variant");
   constexpr bool BWD = MODE == 1, TWO = MODE == 2;
   constexpr int H = 32 * MT, NSUB = 8 / MT, NBUF = MT == 8 ? 2 : 1, SUB = MT * 128, BUF = 3 * PANEL_FRAGS;
   extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -236,6 +250,55 @@ __global__ __launch_bounds__(WG_THREADS, MT == 8 ? 1 : 2) void k_panel_rect(
 #pragma unroll
       for (int R = 0; R < NR; ++R) ad[R] = rstd * (ad[R] - s1 - xh[R] * s2);
       atl_store<H>(xo, slab, lane, ad);
+    } else if constexpr (ACT != 0 && !BWD) {  // elementwise.hip's k_act_ln_fwd on the accumulators
+#pragma clang fp contract(off)
+      float v[NR];
+      float sum = 0.f;
+#pragma unroll
+      for (int R = 0; R < NR; ++R) {
+        v[R] = act_value(acc[R >> 4][R & 15], ACT);
+        sum += v[R];
+      }
+      sum = wave_sum32(sum);
+      const float mean = sum * (1.0f / H);
+      float vs = 0.f;
+#pragma unroll
+      for (int R = 0; R < NR; ++R) {
+        v[R] -= mean;
+        vs += v[R] * v[R];
+      }
+      vs = wave_sum32(vs);
+      const float rstd = 1.0f / sqrtf(vs * (1.0f / H) + 1e-5f);
+#pragma unroll
+      for (int R = 0; R < NR; ++R) v[R] *= rstd;
+      atl_store<H>(xo, slab, lane, v);
+      if (lane < 32) {
+        per_iteration(mean_out)[slab * SLAB + lane] = mean;
+        per_iteration(rstd_out)[slab * SLAB + lane] = rstd;
+      }
+    } else if constexpr (ACT != 0) {  // ln_bwd_relu_mbits without the mask words, then k_act_bwd's slope on its output
+      float xh[NR], out[NR];
+      atl_load<H>(per_iteration(xprev), slab, lane, xh);
+      const float rstd = per_iteration(rstd_prev)[slab * SLAB + i], mean = per_iteration(mean_prev)[slab * SLAB + i];
+      float s1 = 0.f, s2 = 0.f;
+#pragma unroll
+      for (int R = 0; R < NR; ++R) {
+        const float d = acc[R >> 4][R & 15];
+        s1 += d;
+        s2 = __builtin_fmaf(d, xh[R], s2);
+      }
+      s1 = wave_sum32(s1);
+      s2 = wave_sum32(s2);
+      const float c1 = -(s1 * (1.0f / H)) * rstd, c2 = -(s2 * (1.0f / H)) * rstd;
+#pragma unroll
+      for (int R = 0; R < NR; ++R) out[R] = __builtin_fmaf(xh[R], c2, __builtin_fmaf(acc[R >> 4][R & 15], rstd, c1));
+      {
+#pragma clang fp contract(off)
+        const float sd = 1.0f / rstd;
+#pragma unroll
+        for (int R = 0; R < NR; ++R) out[R] *= act_slope_from_value(xh[R] * sd + mean, ACT);
+      }
+      atl_store<H>(xo, slab, lane, out);
     } else if constexpr (!BWD) {
       uint32_t *mo = per_iteration(mask_out);
       float *ro = per_iteration(rstd_out);
@@ -285,6 +348,32 @@ void launch_rect(const float *xin, int KP, const float *Wp, int ldw, int kvalid,
   allow_big_lds(k_panel_rect<MT, MODE>, shm);
   hipLaunchKernelGGL((k_panel_rect<MT, MODE>), dim3(persistent_grid(n_slabs, WG_PER_CU)), dim3(WG_THREADS), shm, s, xin, KP, Wp,
                      ldw, kvalid, bp, xout, mask_out, rstd_out, xprev, mask_prev, rstd_prev, n_slabs, xin2, W2, ld2, n_first);
+}
+
+// the ACT = 1..4 instantiations (MODE 0 / 1): the ReLU launch's geometry as it stands, mean in the place of the mask words
+template <int MT, int MODE, int ACT>
+void launch_rect_act(const float *xin, int KP, const float *Wp, int ldw, int kvalid, const float *bp, float *xout, float *mean_out,
+                     float *rstd_out, const float *xprev, const float *mean_prev, const float *rstd_prev, long n_slabs, hipStream_t s) {
+  constexpr int NBUF = MT == 8 ? 2 : 1, WG_PER_CU = MT == 8 ? 1 : 2;
+  const size_t shm = (size_t)NBUF * 3 * PANEL_FRAGS * sizeof(u32x4);
+  allow_big_lds(k_panel_rect<MT, MODE, ACT>, shm);
+  hipLaunchKernelGGL((k_panel_rect<MT, MODE, ACT>), dim3(persistent_grid(n_slabs, WG_PER_CU)), dim3(WG_THREADS), shm, s, xin, KP, Wp,
+                     ldw, kvalid, bp, xout, (uint32_t *)nullptr, rstd_out, xprev, (const uint32_t *)nullptr, rstd_prev, n_slabs,
+                     (const float *)nullptr, (const float *)nullptr, 0, 0, mean_out, mean_prev);
+}
+
+// ... by run-time width and activation id (both checked by the caller)
+template <int MODE, typename... Args>
+void dispatch_rect_act(int H, int act, Args... a) {
+#define RECT_ACT(MTv)                                            \
+  switch (act) {                                                 \
+    case 1: launch_rect_act<MTv, MODE, 1>(a...); break;          \
+    case 2: launch_rect_act<MTv, MODE, 2>(a...); break;          \
+    case 3: launch_rect_act<MTv, MODE, 3>(a...); break;          \
+    default: launch_rect_act<MTv, MODE, 4>(a...); break;         \
+  }
+  if (H == 64) { RECT_ACT(2) } else if (H == 128) { RECT_ACT(4) } else { RECT_ACT(8) }
+#undef RECT_ACT
 }
 
 bool width_ok(int h) { return h == 64 || h == 128 || h == 256; }
@@ -677,6 +766,28 @@ extern "C" int harl_mlp_rect_bwd(const float *dz, const float *xprev, const uint
   if (HI == 64) RECT(2); else if (HI == 128) RECT(4); else RECT(8);
 #undef RECT
   return check_launch("harl_mlp_rect_bwd");
+}
+
+extern "C" int harl_mlp_rect_act_fwd(const float *xin, long M, int KP, const float *Wp, int D, const float *bp, int HO, int act,
+                                     float *xout, float *mean, float *rstd, void *stream) {
+  if (M <= 0) return 0;
+  if (act < 1 || act > 4) return bad("harl_mlp_rect_act_fwd: activation id must be 1 (leaky_relu), 2 (tanh), 3 (sigmoid) or 4 (selu)");
+  if (!width_ok(HO)) return bad("harl_mlp_rect_act_fwd: output width must be 64, 128 or 256");
+  if (D < 1 || KP % 32 != 0 || KP < D || KP > 512) return bad("harl_mlp_rect_act_fwd: KP must be a multiple of 32, >= D >= 1 and <= 512");
+  dispatch_rect_act<0>(HO, act, xin, KP, Wp, D, D, bp, xout, mean, rstd, (const float *)nullptr, (const float *)nullptr,
+                       (const float *)nullptr, n_slabs_of(M), (hipStream_t)stream);
+  return check_launch("harl_mlp_rect_act_fwd");
+}
+
+extern "C" int harl_mlp_rect_act_bwd(const float *dz, const float *xprev, const float *mean_prev, const float *rstd_prev, long M,
+                                     int HO, int HI, int act, const float *Wp, float *dz_prev, void *stream) {
+  if (M <= 0) return 0;
+  if (act < 1 || act > 4) return bad("harl_mlp_rect_act_bwd: activation id must be 1 (leaky_relu), 2 (tanh), 3 (sigmoid) or 4 (selu)");
+  if (!width_ok(HO) || !width_ok(HI)) return bad("harl_mlp_rect_act_bwd: both widths must be 64, 128 or 256");
+  // (rows = input features, k = output features, as in harl_mlp_rect_bwd)
+  dispatch_rect_act<1>(HI, act, dz, HO, Wp, HI, HO, (const float *)nullptr, dz_prev, (float *)nullptr, (float *)nullptr, xprev,
+                       mean_prev, rstd_prev, n_slabs_of(M), (hipStream_t)stream);
+  return check_launch("harl_mlp_rect_act_bwd");
 }
 
 extern "C" int harl_mlp_rect_tangent(const float *xin_dot, const float *xin, long M, int KP, int HO, const float *Wp,

@@ -18,7 +18,7 @@ import torch
 from . import _lib
 from ._lib import call, ptr, stream
 from .buffers import OnPolicyActorBuffer, consume_randperm, rng_sync
-from .configs import (CAT_WIDE_REFUSALS, GAUSS_WIDE_REFUSALS, MIXED_256_REFUSALS, gauss_wide_enabled, is_mixed_256,
+from .configs import (ACT_256_REFUSALS, CAT_WIDE_REFUSALS, GAUSS_WIDE_REFUSALS, MIXED_256_REFUSALS, act_256_applies, gauss_wide_enabled, is_mixed_256,
                       mixed_256_enabled, trpo_cat_wide_256_enabled, trpo_cat_wide_enabled, trpo_mixed_256_enabled)
 from .happo import OnPolicyBase
 from .nets import build_seq, consume_policy_init_rng, seq_compact
@@ -36,6 +36,8 @@ class HATRPO(OnPolicyBase):
             raise NotImplementedError(GAUSS_WIDE_REFUSALS["hatrpo" if int(act_space.shape[0]) <= 64 else "n"])
         if is_mixed_256(list(args["hidden_sizes"])) and mixed_256_enabled() and not trpo_mixed_256_enabled():
             raise NotImplementedError(MIXED_256_REFUSALS["hatrpo"])  # (the tangent of a rectangular pair is opt-in: _fvp)
+        if act_256_applies(list(args["hidden_sizes"]), args.get("activation_func", "relu")):
+            raise NotImplementedError(ACT_256_REFUSALS["hatrpo"])  # (HARL_ACT_256=1: k_panel_rect's tangent has no activation variant)
         super().__init__(args, obs_space, act_space, device)  # (HARL_TRPO_CAT_WIDE=1: n > 512, 256-wide and non-ReLU are refused there)
         if self.actor.cat_wide and self.actor.recurrent and self.actor.gru_wide:
             raise NotImplementedError(CAT_WIDE_REFUSALS["hatrpo_gru_wide"])

@@ -23,8 +23,9 @@ import torch.nn as nn
 from . import _lib
 from . import graphs as _graphs
 from ._lib import DHEAD_LD, PS_STRIDE, SLAB, call, ptr, stream
-from .configs import (GAUSS_WIDE_REFUSALS, bwd_k64, bwd_streams, cat_wide_reason, gauss_wide_enabled, gauss_wide_reason, gru_dw6,
-                      is_mixed_256, mixed_256_enabled, mixed_256_reason, trunk_dw_stream)
+from .configs import (ACT_256_REFUSALS, GAUSS_WIDE_REFUSALS, act_256_applies, act_256_reason, bwd_k64, bwd_streams, cat_wide_reason,
+                      gauss_wide_enabled, gauss_wide_reason, gru_dw6, is_mixed_256, mixed_256_enabled, mixed_256_reason,
+                      trunk_dw_stream)
 
 SUPPORTED_WIDTHS = (64, 128, 256)
 # models_tools.py:28-50; ids of csrc/elementwise.hip (0 = the fused ReLU kernels)
@@ -169,6 +170,8 @@ class _FlatNet(nn.Module):
         # fused kernels and their goldens (tests only)
         if self.recurrent and hl == 64 and os.environ.get("HARL_GRU_COMPOSED") == "1":
             self.gru_wide = True
+        if self.recurrent and not is_mixed_256(self.hidden_sizes) and act_256_applies(self.hidden_sizes, self.activation_func):
+            raise NotImplementedError(act_256_reason(recurrent=True))  # (in front of the GRU's own width check, as unsupported_reason has it)
         if self.recurrent and self.recurrent_n < 1:
             raise ValueError("recurrent_n must be >= 1")
         if self.recurrent and not self.gru_wide and (hl != 64 or self.recurrent_n != 1):
@@ -180,13 +183,17 @@ class _FlatNet(nn.Module):
         # HARL_MIXED_256=1, 256-wide layers next to 64- / 128-wide ones on the same layer-by-layer route (csrc/rect.hip)
         self.panel = 256 in self.hidden_sizes
         self.mixed_256 = is_mixed_256(self.hidden_sizes) and mixed_256_enabled()
-        if self.mixed_256:
-            why = mixed_256_reason(self.hidden_sizes, self.activation_func, self.recurrent, in_dim)
-            if why is not None:
-                raise NotImplementedError(why)
-        elif self.panel and (any(h != 256 for h in self.hidden_sizes) or self.recurrent or in_dim > 512):
+        # HARL_ACT_256=1: a non-ReLU activation on such a trunk -- EVERY layer on csrc/rect.hip's kernels with the activation and the
+        # LayerNorm in their epilogue (harl_mlp_rect_act_fwd / _bwd; forward_trunk's panel branch, _backward_panel)
+        self.act_256 = act_256_applies(self.hidden_sizes, self.activation_func)
+        why = mixed_256_reason(self.hidden_sizes, self.activation_func, self.recurrent, in_dim) if self.mixed_256 else None
+        if why is None and self.act_256:
+            why = act_256_reason(recurrent=self.recurrent, in_dim=in_dim)
+        if why is not None:
+            raise NotImplementedError(why)
+        if self.panel and not self.mixed_256 and (any(h != 256 for h in self.hidden_sizes) or self.recurrent or in_dim > 512):
             raise NotImplementedError("hidden width 256: all layers must be 256 wide, feed-forward, inputs <= 512")
-        if self.act_id and (self.recurrent or self.panel or in_dim > 512):
+        if self.act_id and not self.act_256 and (self.recurrent or self.panel or in_dim > 512):
             raise NotImplementedError("activation functions other than relu: feed-forward MLPs of width 64 / 128 with inputs <= 512")
         self.in_dim = in_dim
         self.wide = 32 < in_dim <= 512  # first layer through the cached x0n image (csrc/wide.hip); <= 32: fused 2-layer kernel
@@ -444,12 +451,14 @@ class _FlatNet(nn.Module):
         self._x0n_key = None
         self.x0n = torch.empty(mp * self.kp0, dtype=f32, device=dev) if self.has_x0n else None
         self.w1img = (torch.empty(3 * self.hidden_sizes[0] * self.kp0 // 2, dtype=f32, device=dev)
-                      if (self.wide or self.act_id) else None)
+                      if (self.wide or (self.act_id and not self.act_256)) else None)
         hmax = max(self.hidden_sizes)
         if self.act_id:  # composed activation path: raw pre-activations, mean(act(z)) per layer, an all-ones "ReLU mask"
-            self.zraw = torch.empty(mp * hmax, dtype=f32, device=dev)
+            if not self.act_256:  # (the epilogues of harl_mlp_rect_act_fwd / _bwd: no pre-activation image)
+                self.zraw = torch.empty(mp * hmax, dtype=f32, device=dev)
             self.amean = [torch.empty(mp, dtype=f32, device=dev) for _ in self.hidden_sizes]
-            self.ones_mask = torch.full((n_slabs * 64 * 2,), -1, dtype=u32, device=dev)
+            # (H / 2 + 31) / 32 words per lane at the head input: two up to 128 columns, four at 256
+            self.ones_mask = torch.full((n_slabs * 64 * (4 if self.hidden_sizes[-1] == 256 else 2),), -1, dtype=u32, device=dev)
         # ping-pong, ATL; a third one where the one-launch trunk backward keeps every layer's dz for the weight-gradient launch
         self.dz = [torch.empty(mp * hmax, dtype=f32, device=dev) for _ in range(3 if len(self.hidden_sizes) == 3 and self.trunk_fused() else 2)]
         # head gradients for the separate dW pass: row-major [mp][32], or the ATL(64) image of a 33..64-way Categorical head
@@ -576,7 +585,7 @@ class _FlatNet(nn.Module):
         only), so prepare_x0n in front of a captured step need not know.  Host path of every forward: comparisons only."""
         hs = self.hidden_sizes
         two_equal = len(hs) >= 2 and hs[0] == hs[1]
-        return _ROUTES["act" if self.act_id else
+        return _ROUTES["act" if self.act_id and not self.panel else  # (HARL_ACT_256=1: "panel", as in _backward_route)
                        "panel" if self.panel else
                        "trunk" if not partial and self.trunk_fused() else
                        "fused2x" if two_equal and self.in_dim <= 64 and idx_is_none else
@@ -651,6 +660,10 @@ class _FlatNet(nn.Module):
             for l in range(len(hs)):
                 Wp, bp = self._packs[l]
                 xin, kp, d = (self.x0n, self.kp0, self.in_dim) if l == 0 else (self.xh[l - 1], hs[l - 1], hs[l - 1])
+                if self.act_id:  # every layer, first and 256 -> 256 included: activation + LayerNorm in the rectangular kernel's epilogue
+                    call("harl_mlp_rect_act_fwd", ptr(xin), M, kp, ptr(Wp), d, ptr(bp), hs[l], self.act_id, ptr(self.xh[l]),
+                         ptr(self.amean[l]), ptr(self.rstd[l]), s, tag="fwd_rect_act")
+                    continue
                 # (the first layer and 256 -> 256 as on all-256 trunks; every other pair of widths on the rectangular kernel)
                 square = hs[l] == 256 and (l == 0 or hs[l - 1] == 256)
                 name, tag = ("harl_mlp_panel_fwd", "fwd_panel") if square else ("harl_mlp_rect_fwd", "fwd_rect")
@@ -909,12 +922,21 @@ class _FlatNet(nn.Module):
 
     def _backward_panel(self, M: int, s) -> None:
         """Width 256 (csrc/panel.hip; csrc/rect.hip where one side of a layer is narrower): per layer dW = dz^T x_hat_prev, then
-        dz_prev through the panel GEMM."""
+        dz_prev through the panel GEMM.  Activation other than ReLU: the loss kernel was handed the all-ones mask (feat) and left
+        d(loss)/d(act(z_L)), harl_act_bwd multiplies the top layer's act' in as in _backward_act; below it act' is part of the
+        epilogue of harl_mlp_rect_act_bwd."""
         hs, cur = self.hidden_sizes, 0
+        if self.act_id:
+            call("harl_act_bwd", ptr(self.dz[cur]), ptr(self.xh[-1]), ptr(self.amean[-1]), ptr(self.rstd[-1]), M, hs[-1], self.act_id,
+                 s, tag="act_bwd")
         for l in range(len(hs) - 1, -1, -1):
             b_in, k_in = (self.x0n, self.kp0) if l == 0 else (self.xh[l - 1], hs[l - 1])
             self._dw_atl(self.dz[cur], hs[l], b_in, k_in, M, l, s, "dw_hidden" if l else "dw_input")
-            if l > 0:
+            if l > 0 and self.act_id:
+                call("harl_mlp_rect_act_bwd", ptr(self.dz[cur]), ptr(self.xh[l - 1]), ptr(self.amean[l - 1]), ptr(self.rstd[l - 1]), M,
+                     hs[l], hs[l - 1], self.act_id, ptr(self._packs[l][0]), ptr(self.dz[1 - cur]), s, tag="bwd_rect_act")
+                cur = 1 - cur
+            elif l > 0:
                 Wp, _ = self._packs[l]
                 name, tag = ("harl_mlp_panel_bwd", "bwd_panel") if hs[l] == hs[l - 1] == 256 else ("harl_mlp_rect_bwd", "bwd_rect")
                 call(name, ptr(self.dz[cur]), ptr(self.xh[l - 1]), ptr(self.rmask[l - 1]),
@@ -1265,6 +1287,8 @@ class StochasticPolicy(_FlatNet):
         """Heads in the reference's order (same RNG draws), packed first-fit IN ORDER into groups of <= 128 logits; a group is
         one contiguous [S_g, d] block of the arena so that fold / weight-gradient / Adam see it as a single Linear."""
         nvec = [int(n) for n in action_space.nvec]
+        if self.act_256:
+            raise NotImplementedError(ACT_256_REFUSALS["md"])
         if self.panel:
             raise NotImplementedError("MultiDiscrete heads on 256-wide layers")
         if len(nvec) > 8 or max(nvec) > 128:

@@ -238,6 +238,17 @@ def _panel_bwd(a: Sequence) -> float:  # (dz, xprev, relu_mask_prev, rstd_prev, 
     return a[4] * (4.0 * a[5] + _act(a[6]) + 4.0 * a[6])
 
 
+def _rect_act_fwd(a: Sequence) -> float:
+    # (xin, M, KP, Wp, D, bp, HO, act, xout, mean, rstd, stream): the input image, x_hat out, mean and rstd per row -- no mask
+    # words, and no pre-activation image (the composed route's harl_mlp_linear + harl_act_ln_fwd move 8 HO bytes more per row)
+    return a[1] * (4.0 * a[2] + 4.0 * a[6] + 8.0)
+
+
+def _rect_act_bwd(a: Sequence) -> float:
+    # (dz, xprev, mean_prev, rstd_prev, M, HO, HI, act, Wp, dz_prev, stream): dz, the record of the layer below, dz_prev out
+    return a[4] * (4.0 * a[5] + 4.0 * a[6] + 8.0 + 4.0 * a[6])
+
+
 def _tangent_hidden(a: Sequence) -> float:
     # (xin_dot, xin, M, HI, HO, Wp, Wdp, bdp, xprimal, mask_in, rstd_in, xout_dot, stream): both inputs, the primal x_hat / mask /
     # rstd of the layer, the tangent out (the raw intermediate of the two-GEMM formulation is traffic, not algorithm)
@@ -308,6 +319,8 @@ ALGORITHMIC_BYTES: Dict[str, Callable[[Sequence], float]] = {
     "harl_mlp_panel_bwd": _panel_bwd,
     "harl_mlp_rect_fwd": _panel_fwd,  # (csrc/rect.hip: the same arguments, the same bytes per row)
     "harl_mlp_rect_bwd": _panel_bwd,
+    "harl_mlp_rect_act_fwd": _rect_act_fwd,
+    "harl_mlp_rect_act_bwd": _rect_act_bwd,
     "harl_mlp_rect_tangent": _tangent_rect,
     "harl_mlp_rect_linear_groups": _linear_groups,
     "harl_mlp_rect_bwd_groups": _bwd_groups,
@@ -439,6 +452,8 @@ ALGORITHMIC_FLOPS: Dict[str, Callable[[Sequence], float]] = {
     "harl_mlp_panel_bwd": lambda a: 2.0 * a[4] * a[5] * a[6],
     "harl_mlp_rect_fwd": lambda a: 2.0 * a[1] * a[4] * a[6],
     "harl_mlp_rect_bwd": lambda a: 2.0 * a[4] * a[5] * a[6],
+    "harl_mlp_rect_act_fwd": lambda a: 2.0 * a[1] * a[4] * a[6],
+    "harl_mlp_rect_act_bwd": lambda a: 2.0 * a[4] * a[5] * a[6],
     "harl_mlp_rect_tangent": lambda a: 2.0 * (2 if a[0] else 1) * a[2] * a[7] * a[4],  # one GEMM for a first layer, two for a hidden one
     "harl_mlp_rect_linear_groups": lambda a: 2.0 * a[1] * a[2] * sum(a[4][g] for g in range(a[3])),
     "harl_mlp_rect_bwd_groups": lambda a: 2.0 * a[7] * a[8] * sum(a[2][g] for g in range(a[1])),

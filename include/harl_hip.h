@@ -209,6 +209,19 @@ int harl_mlp_rect_fwd(const float *xin, long M, int KP, const float *Wp, int D, 
                       uint32_t *relu_mask, float *rstd, void *stream);
 int harl_mlp_rect_bwd(const float *dz, const float *xprev, const uint32_t *relu_mask_prev, const float *rstd_prev, long M,
                       int HO, int HI, const float *Wp, float *dz_prev, void *stream);
+/* The same layers with an activation other than ReLU (mlp.py:19-38 with models_tools.py:28-50; opt-in HARL_ACT_256=1): act = 1
+ * leaky_relu, 2 tanh, 3 sigmoid, 4 selu, the ids of harl_act_ln_fwd.  k_panel_rect<MT, MODE, ACT>: the walk of the two kernels
+ * above with the activation, the LayerNorm and their backward in the epilogue, on the accumulators -- no pre-activation image
+ * crosses HBM as it does between harl_mlp_linear and harl_act_ln_fwd / harl_mlp_bwd_dx and harl_act_bwd.
+ *   harl_mlp_rect_act_fwd: xout = norm(act(Wp xin + bp)); the record is xout, mean = mean_f(act(z)) and rstd per row, no mask.
+ *   harl_mlp_rect_act_bwd: dz_prev = act'(a) . LNbwd(Wp^T dz) with a = xprev / rstd_prev + mean_prev and act' taken from that
+ *     value, as harl_act_bwd does.  Rows past M of the last slab: dz_prev is 0 where dz is.
+ * Shapes as for harl_mlp_rect_fwd / harl_mlp_rect_bwd (every pair of widths, first layers included); other shapes or another
+ * act: -2 and an error text.  Nothing is allocated, nothing synchronises.  The top layer's act' is harl_act_bwd, which takes H = 256 as well. */
+int harl_mlp_rect_act_fwd(const float *xin, long M, int KP, const float *Wp, int D, const float *bp, int HO, int act, float *xout,
+                          float *mean, float *rstd, void *stream);
+int harl_mlp_rect_act_bwd(const float *dz, const float *xprev, const float *mean_prev, const float *rstd_prev, long M, int HO,
+                          int HI, int act, const float *Wp, float *dz_prev, void *stream);
 /* Forward-mode tangent of such a layer (HATRPO's Fisher-vector product, trpo_util.py:132-158 -- the reference's double backward
  * through MLPBase, mlp.py:7-70 -- on the trunks above; opt-in HARL_TRPO_MIXED_256=1 next to HARL_MIXED_256=1):
  * x_out_dot = LNjac(mask . (Wdp x_in + bdp [+ Wp x_in_dot])) with the PRIMAL x_hat / mask / rstd of this layer, arguments and
@@ -502,7 +515,7 @@ int harl_mlp_tangent_input(const float *X, long ldx, const int64_t *idx, long M,
 int harl_mlp_linear_wide(const float *x0n, long M, int KP, const float *Wp, int D, const float *bp, int H, void *w_img,
                          float *zout, void *stream);
 /* Activation functions other than ReLU (models_tools.py:28-50; act: 1 leaky_relu, 2 tanh, 3 sigmoid, 4 selu), element-wise
- * over ATL(H) images, H = 64 / 128.  harl_act_ln_fwd: x_hat = LayerNorm(act(z)) with mean(act(z)) and rstd per sample
+ * over ATL(H) images, H = 64 / 128 (harl_act_bwd: also 256, the top layer behind harl_mlp_rect_act_bwd).  harl_act_ln_fwd: x_hat = LayerNorm(act(z)) with mean(act(z)) and rstd per sample
  * (mlp.py:25-38).  harl_act_bwd: dz <- dz * act'(z) in place, act' from the activation value x_hat / rstd + mean; dz holds
  * the LayerNorm backward as harl_mlp_bwd_dx / the loss kernels leave it when they are given an all-ones ReLU mask. */
 int harl_act_ln_fwd(const float *z, long M, int H, int act, float *xhat, float *mean, float *rstd, void *stream);

@@ -179,6 +179,17 @@ def main():
         ("h17_cat512_linear_x8", eight_linear, GF(8 * fl2)),
         ("h17_cat512_tangent_groups_K256", lambda: call("harl_mlp_rect_tangent_groups", ptr(yb), ptr(ya), B2, 256, 4, sp4, Ws256, Wds256, bs4, zs4, s), GF(16 * fl2)),
     ]
+    # ---- HARL_ACT_256=1: k_panel_rect<MT, MODE, ACT> with the tanh epilogue next to the ReLU launch of the same shape and rows
+    # (filter "rect_relu" with --lib on another build: the yardstick of profiles/r21_act_256.md)
+    rstd_o, mean_o = torch.empty(mp2, device=dev), torch.zeros(mp2, device=dev)
+    for hi, ho in ((256, 128), (128, 256), (256, 256)):
+        f = GF(2.0 * B2 * hi * ho)
+        jobs += [
+            (f"h17_rect_relu_fwd_{hi}to{ho}", lambda hi=hi, ho=ho: call("harl_mlp_rect_fwd", ptr(ya), B2, hi, ptr(Wr), hi, ptr(br), ho, ptr(yo), ptr(mask4_), ptr(rstd_o), s), f),
+            (f"h17_rect_tanh_fwd_{hi}to{ho}", lambda hi=hi, ho=ho: call("harl_mlp_rect_act_fwd", ptr(ya), B2, hi, ptr(Wr), hi, ptr(br), ho, 2, ptr(yo), ptr(mean_o), ptr(rstd_o), s), f),
+            (f"h17_rect_relu_bwd_{ho}to{hi}", lambda hi=hi, ho=ho: call("harl_mlp_rect_bwd", ptr(yb), ptr(ya), ptr(mask4_), ptr(rstd2_), B2, ho, hi, ptr(Wr), ptr(yo), s), f),
+            (f"h17_rect_tanh_bwd_{ho}to{hi}", lambda hi=hi, ho=ho: call("harl_mlp_rect_act_bwd", ptr(yb), ptr(ya), ptr(mean_o), ptr(rstd2_), B2, ho, hi, 2, ptr(Wr), ptr(yo), s), f),
+        ]
     print(f"B={B}  H={H}  reps={args.reps}  lib={_lib.LIB_PATH}")
     for name, fn, (unit, work) in jobs:
         if args.filters and not any(f in name for f in args.filters):
