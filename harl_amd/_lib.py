@@ -113,6 +113,7 @@ SIGNATURES = {
     "harl_mlp_rect_act_fwd": [_vp, _l, _i, _vp, _i, _vp, _i, _i, _vp, _vp, _vp, _vp],
     "harl_mlp_rect_act_bwd": [_vp, _vp, _vp, _vp, _l, _i, _i, _i, _vp, _vp, _vp],
     "harl_mlp_rect_tangent": [_vp, _vp, _l, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp],
+    "harl_mlp_rect_act_tangent": [_vp, _vp, _l, _i, _i, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp],
     "harl_mlp_rect_linear_groups": [_vp, _l, _i, _i, _vp, _vp, _vp, _vp, _vp],
     "harl_mlp_rect_bwd_groups": [_vp, _i, _vp, _vp, _vp, _vp, _vp, _l, _i, _vp, _vp],
     "harl_mlp_rect_tangent_groups": [_vp, _vp, _l, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp],

@@ -30,7 +30,8 @@
 //   tangent  : x_out_dot = LNjac(mask . (W'_dot x_in + b'_dot [+ W' x_in_dot]))   HATRPO's Fisher-vector product on these trunks
 //              (opt-in HARL_TRPO_MIXED_256=1): both products are ONE stream of sub-panels through the same prefetch pipeline
 //   ACT 1..4 : forward x_hat_out = norm(act(W' x_in + b')), backward dz_in = act'(a) . LNbwd(W'^T dz_out) for leaky_relu / tanh /
-//              sigmoid / selu (opt-in HARL_ACT_256=1): the same walk, another epilogue (see k_panel_rect)
+//              sigmoid / selu (opt-in HARL_ACT_256=1): the same walk, another epilogue (see k_panel_rect); tangent x_out_dot =
+//              LNjac(act'(a) . (W'_dot x_in + b'_dot [+ W' x_in_dot])) (opt-in HARL_TRPO_ACT_256=1): MODE 2's stream, another epilogue
 // The GEMM is split_mfma.h's exact three-term bf16 split, six products, fp32 accumulation; x_hat / ReLU mask words / rstd
 // leave in the layouts of the 64 / 128-wide layer kernels (fwd_epilogue.h) and of k_panel, so the head kernels,
 // harl_mlp_dw_partials and harl_mlp_bwd_dx read them unchanged.  Rows past M inside the last slab are computed like any
@@ -157,7 +158,7 @@ __device__ __forceinline__ T *per_iteration(T *p) {
 //   boundary (MT = 2, 64 -> 64: the whole K = 128 reduction is ONE panel), and there is no drain between the operands.  n_first
 //   counts the sub-panels that hold a valid column of Wp; the columns of x_in past them would meet zero weights and are skipped.
 //
-// ACT 0 is ReLU, everything above.  ACT 1..4 (act_funcs.h: leaky_relu, tanh, sigmoid, selu; MODE 0 / 1, opt-in HARL_ACT_256=1) changes
+// ACT 0 is ReLU, everything above.  ACT 1..4 (act_funcs.h: leaky_relu, tanh, sigmoid, selu; opt-in HARL_ACT_256=1) changes
 // the EPILOGUE only, where every accumulator of the slab already sits in this wave's registers -- the composed 64 / 128 route
 // (raw GEMM, harl_act_ln_fwd, harl_act_bwd) sends the pre-activation image through HBM for the same arithmetic:
 //   forward  : a = act(acc), x_hat = LayerNorm(a) in the two-pass form below; the record is x_hat, mean(a), rstd (mean_out,
@@ -165,6 +166,12 @@ __device__ __forceinline__ T *per_iteration(T *p) {
 //   backward : dz_prev = act'(a) . LNbwd(W'^T dz) with act' taken from the value a (mean_prev, rstd_prev), multiplied into the
 //              LayerNorm backward's output in place: at MT = 8 nothing joins acc / x_hat / out, the three 128-register arrays
 //              live at the ReLU epilogue's peak.  A zero dz row still gives a zero row (0 times a finite slope).
+//   tangent  : (HATRPO on these networks, opt-in HARL_TRPO_ACT_256=1) the K loop is MODE 2's, two operands in one stream; the
+//              epilogue rebuilds a from the same record with the backward's own arithmetic -- the slope the Fisher-vector
+//              product's forward half multiplies by is bit for bit the one its backward half multiplies by -- and multiplies
+//              act'(a) into the ACCUMULATORS in place, where the ReLU tangent pops mask bits; the LayerNorm Jacobian then runs on
+//              them as it does there (acc / x_hat / out at MT = 8 again).  No mask words are read.  The composed 64 / 128 route
+//              (two raw harl_mlp_linear, harl_act_ln_tangent) is three launches and two pre-activation images through HBM.
 template <int MT, int MODE, int ACT = 0>
 __global__ __launch_bounds__(WG_THREADS, MT == 8 ? 1 : 2) void k_panel_rect(
     const float *__restrict__ xin, int KP, const float *__restrict__ Wp, int ldw, int kvalid, const float *__restrict__ bp,
@@ -172,7 +179,7 @@ __global__ __launch_bounds__(WG_THREADS, MT == 8 ? 1 : 2) void k_panel_rect(
     const uint32_t *__restrict__ mask_prev, const float *__restrict__ rstd_prev, long n_slabs,
     const float *__restrict__ xin2 = nullptr, const float *__restrict__ W2 = nullptr, int ld2 = 0, int n_first = 0,
     float *__restrict__ mean_out = nullptr, const float *__restrict__ mean_prev = nullptr) {
-  static_assert(ACT >= 0 && ACT <= 4 && (ACT == 0 || MODE != 2), "the tangent has no activation variant");
+  static_assert(ACT >= 0 && ACT <= 4 && MODE >= 0 && MODE <= 2, "relu and the four of act_funcs.h; forward, backward, tangent");
   constexpr bool BWD = MODE == 1, TWO = MODE == 2;
   constexpr int H = 32 * MT, NSUB = 8 / MT, NBUF = MT == 8 ? 2 : 1, SUB = MT * 128, BUF = 3 * PANEL_FRAGS;
   extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -230,7 +237,29 @@ __global__ __launch_bounds__(WG_THREADS, MT == 8 ? 1 : 2) void k_panel_rect(
     if (!live) continue;
     constexpr int NR = H / 2, NW = (NR + 31) / 32;
     float *xo = per_iteration(xout);
-    if constexpr (TWO) {  // mlp.hip's ln_jac_store on registers: nothing of it is addressed before the panel loop has ended
+    if constexpr (TWO && ACT != 0) {  // the block below with act'(a) from the value record in the place of the mask bits
+      float xh[NR], ad[NR];
+      atl_load<H>(per_iteration(xprev), slab, lane, xh);
+      const float rstd = per_iteration(rstd_prev)[slab * SLAB + i], mean = per_iteration(mean_prev)[slab * SLAB + i];
+      {
+#pragma clang fp contract(off)
+        const float sd = 1.0f / rstd;  // (the backward's rebuild of a, operation for operation)
+#pragma unroll
+        for (int R = 0; R < NR; ++R) acc[R >> 4][R & 15] *= act_slope_from_value(xh[R] * sd + mean, ACT);
+      }
+      float s1 = 0.f, s2 = 0.f;
+#pragma unroll
+      for (int R = 0; R < NR; ++R) {
+        const float d = acc[R >> 4][R & 15];
+        s1 += d;
+        s2 += d * xh[R];
+      }
+      s1 = wave_sum32(s1) * (1.0f / H);
+      s2 = wave_sum32(s2) * (1.0f / H);
+#pragma unroll
+      for (int R = 0; R < NR; ++R) ad[R] = rstd * (acc[R >> 4][R & 15] - s1 - xh[R] * s2);
+      atl_store<H>(xo, slab, lane, ad);
+    } else if constexpr (TWO) {  // mlp.hip's ln_jac_store on registers: nothing of it is addressed before the panel loop has ended
       float xh[NR], ad[NR];
       atl_load<H>(per_iteration(xprev), slab, lane, xh);
       const uint32_t *mi = per_iteration(mask_prev);
@@ -350,16 +379,18 @@ void launch_rect(const float *xin, int KP, const float *Wp, int ldw, int kvalid,
                      ldw, kvalid, bp, xout, mask_out, rstd_out, xprev, mask_prev, rstd_prev, n_slabs, xin2, W2, ld2, n_first);
 }
 
-// the ACT = 1..4 instantiations (MODE 0 / 1): the ReLU launch's geometry as it stands, mean in the place of the mask words
+// the ACT = 1..4 instantiations: the ReLU launch's geometry as it stands, mean in the place of the mask words (MODE 2: the second
+// operand of launch_rect)
 template <int MT, int MODE, int ACT>
 void launch_rect_act(const float *xin, int KP, const float *Wp, int ldw, int kvalid, const float *bp, float *xout, float *mean_out,
-                     float *rstd_out, const float *xprev, const float *mean_prev, const float *rstd_prev, long n_slabs, hipStream_t s) {
+                     float *rstd_out, const float *xprev, const float *mean_prev, const float *rstd_prev, long n_slabs, hipStream_t s,
+                     const float *xin2 = nullptr, const float *W2 = nullptr, int ld2 = 0, int n_first = 0) {
   constexpr int NBUF = MT == 8 ? 2 : 1, WG_PER_CU = MT == 8 ? 1 : 2;
   const size_t shm = (size_t)NBUF * 3 * PANEL_FRAGS * sizeof(u32x4);
   allow_big_lds(k_panel_rect<MT, MODE, ACT>, shm);
   hipLaunchKernelGGL((k_panel_rect<MT, MODE, ACT>), dim3(persistent_grid(n_slabs, WG_PER_CU)), dim3(WG_THREADS), shm, s, xin, KP, Wp,
                      ldw, kvalid, bp, xout, (uint32_t *)nullptr, rstd_out, xprev, (const uint32_t *)nullptr, rstd_prev, n_slabs,
-                     (const float *)nullptr, (const float *)nullptr, 0, 0, mean_out, mean_prev);
+                     xin2, W2, ld2, n_first, mean_out, mean_prev);
 }
 
 // ... by run-time width and activation id (both checked by the caller)
@@ -806,6 +837,23 @@ extern "C" int harl_mlp_rect_tangent(const float *xin_dot, const float *xin, lon
   if (HO == 64) RECT(2); else if (HO == 128) RECT(4); else RECT(8);
 #undef RECT
   return check_launch("harl_mlp_rect_tangent");
+}
+
+extern "C" int harl_mlp_rect_act_tangent(const float *xin_dot, const float *xin, long M, int KP, int HO, const float *Wp,
+                                         const float *Wdp, int D, const float *bdp, int act, const float *xprimal,
+                                         const float *mean_in, const float *rstd_in, float *xout_dot, void *stream) {
+  if (M <= 0) return 0;
+  if (act < 1 || act > 4) return bad("harl_mlp_rect_act_tangent: activation id must be 1 (leaky_relu), 2 (tanh), 3 (sigmoid) or 4 (selu)");
+  if (!width_ok(HO)) return bad("harl_mlp_rect_act_tangent: output width must be 64, 128 or 256");
+  if (xin_dot) {
+    if (!Wp || !width_ok(KP) || D != KP) return bad("harl_mlp_rect_act_tangent: a hidden layer (x_in_dot given) has KP = D = 64, 128 or 256 and needs W'");
+  } else if (D < 1 || KP % 32 != 0 || KP < D || KP > 512) {
+    return bad("harl_mlp_rect_act_tangent: a first layer has KP a multiple of 32, >= D >= 1 and <= 512");
+  }
+  // (harl_mlp_rect_tangent's stream: (D + 31) / 32 sub-panels of W'_dot x_in, then KP / 32 of W' x_in_dot)
+  dispatch_rect_act<2>(HO, act, xin, KP, Wdp, D, D, bdp, xout_dot, (float *)nullptr, (float *)nullptr, xprimal, mean_in, rstd_in,
+                       n_slabs_of(M), (hipStream_t)stream, xin_dot, xin_dot ? Wp : (const float *)nullptr, xin_dot ? KP : 0, (D + 31) / 32);
+  return check_launch("harl_mlp_rect_act_tangent");
 }
 
 extern "C" int harl_mlp_rect_linear_groups(const float *xin, long M, int KP, int n_groups, const int *sp, const float *const *Wp,

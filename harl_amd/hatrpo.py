@@ -19,7 +19,7 @@ from . import _lib
 from ._lib import call, ptr, stream
 from .buffers import OnPolicyActorBuffer, consume_randperm, rng_sync
 from .configs import (ACT_256_REFUSALS, CAT_WIDE_REFUSALS, GAUSS_WIDE_REFUSALS, MIXED_256_REFUSALS, act_256_applies, gauss_wide_enabled, is_mixed_256,
-                      mixed_256_enabled, trpo_cat_wide_256_enabled, trpo_cat_wide_enabled, trpo_mixed_256_enabled)
+                      mixed_256_enabled, trpo_act_256_enabled, trpo_cat_wide_256_enabled, trpo_cat_wide_enabled, trpo_mixed_256_enabled)
 from .happo import OnPolicyBase
 from .nets import build_seq, consume_policy_init_rng, seq_compact
 from .valuenorm import _as_dev
@@ -36,8 +36,8 @@ class HATRPO(OnPolicyBase):
             raise NotImplementedError(GAUSS_WIDE_REFUSALS["hatrpo" if int(act_space.shape[0]) <= 64 else "n"])
         if is_mixed_256(list(args["hidden_sizes"])) and mixed_256_enabled() and not trpo_mixed_256_enabled():
             raise NotImplementedError(MIXED_256_REFUSALS["hatrpo"])  # (the tangent of a rectangular pair is opt-in: _fvp)
-        if act_256_applies(list(args["hidden_sizes"]), args.get("activation_func", "relu")):
-            raise NotImplementedError(ACT_256_REFUSALS["hatrpo"])  # (HARL_ACT_256=1: k_panel_rect's tangent has no activation variant)
+        if act_256_applies(list(args["hidden_sizes"]), args.get("activation_func", "relu")) and not trpo_act_256_enabled():
+            raise NotImplementedError(ACT_256_REFUSALS["hatrpo"])  # (HARL_ACT_256=1 opens these networks to the other algorithms; their tangent, _fvp, is opt-in)
         super().__init__(args, obs_space, act_space, device)  # (HARL_TRPO_CAT_WIDE=1: n > 512, 256-wide and non-ReLU are refused there)
         if self.actor.cat_wide and self.actor.recurrent and self.actor.gru_wide:
             raise NotImplementedError(CAT_WIDE_REFUSALS["hatrpo_gru_wide"])
@@ -126,7 +126,18 @@ class HATRPO(OnPolicyBase):
                      ptr(vec[beo:]) if beo >= 0 else None, ptr(pd[pw:]), ptr(pd[pb:]), o, k, s)
         packs_d = [(pd[pw:pw + o * k], pd[pb:pb + o]) for (pw, pb, o, k) in net._pack_slots]
         Wpd, bpd = packs_d[0]
-        if net.act_id:
+        if net.act_256:
+            # activation other than ReLU on a trunk that holds a 256-wide layer (HARL_TRPO_ACT_256=1; in front of the composed branch
+            # below, whose harl_mlp_linear takes 64 / 128 inputs): EVERY layer, the first and 256 -> 256 included, is one launch of
+            # the rectangular kernel with act' and the LayerNorm Jacobian in its epilogue (csrc/rect.hip) -- no zd images.  x0n,
+            # x_hat_l, mean(a_l), rstd_l of the same rows are still in the workspace from the forward pass of _surrogate().
+            for l in range(L):
+                Wpd, bpd = packs_d[l]
+                xin_dot, xin, kp, Wp, d = ((None, net.x0n, net.kp0, None, net.in_dim) if l == 0 else
+                                           (ws["xd"][l - 1], net.xh[l - 1], hs[l - 1], net._packs[l][0], hs[l - 1]))
+                call("harl_mlp_rect_act_tangent", ptr(xin_dot), ptr(xin), m, kp, hs[l], ptr(Wp), ptr(Wpd), d, ptr(bpd), net.act_id,
+                     ptr(net.xh[l]), ptr(net.amean[l]), ptr(net.rstd[l]), ptr(ws["xd"][l]), s, tag="tangent_rect_act")
+        elif net.act_id:
             # activation other than ReLU (round 4): the tangent of [Linear, act, LayerNorm] composed like the forward pass -- raw
             # GEMMs for the two halves of the pre-activation's tangent, one element-wise launch for act' and the LayerNorm
             # tangent (harl_act_ln_tangent).  x0n, x_hat_l, mean(a_l), rstd_l of the same rows are still in the workspace

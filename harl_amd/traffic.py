@@ -261,6 +261,13 @@ def _tangent_rect(a: Sequence) -> float:
     return a[2] * (4.0 * a[3] * (2 if a[0] else 1) + _act(a[4]) + 4.0 * a[4])
 
 
+def _tangent_rect_act(a: Sequence) -> float:
+    # (xin_dot, xin, M, KP, HO, Wp, Wdp, D, bdp, act, xprimal, mean_in, rstd_in, xout_dot, stream), tag tangent_rect_act: the input
+    # image (and its tangent, for a hidden layer), the primal x_hat / mean / rstd of the layer, the tangent out -- no mask words,
+    # and none of the two pre-activation tangent images the composed route writes and reads again (16 HO bytes more per row)
+    return a[2] * (4.0 * a[3] * (2 if a[0] else 1) + 4.0 * a[4] + 8.0 + 4.0 * a[4])
+
+
 def _linear_groups(a: Sequence) -> float:
     # (xin, M, KP, n_groups, sp, Wp, bp, z, stream), tag md_linear_groups: the head input once (the re-reads per group are L2
     # hits, traffic but not algorithm), every logits image out
@@ -322,6 +329,7 @@ ALGORITHMIC_BYTES: Dict[str, Callable[[Sequence], float]] = {
     "harl_mlp_rect_act_fwd": _rect_act_fwd,
     "harl_mlp_rect_act_bwd": _rect_act_bwd,
     "harl_mlp_rect_tangent": _tangent_rect,
+    "harl_mlp_rect_act_tangent": _tangent_rect_act,
     "harl_mlp_rect_linear_groups": _linear_groups,
     "harl_mlp_rect_bwd_groups": _bwd_groups,
     "harl_mlp_rect_tangent_groups": _tangent_groups,
@@ -455,6 +463,7 @@ ALGORITHMIC_FLOPS: Dict[str, Callable[[Sequence], float]] = {
     "harl_mlp_rect_act_fwd": lambda a: 2.0 * a[1] * a[4] * a[6],
     "harl_mlp_rect_act_bwd": lambda a: 2.0 * a[4] * a[5] * a[6],
     "harl_mlp_rect_tangent": lambda a: 2.0 * (2 if a[0] else 1) * a[2] * a[7] * a[4],  # one GEMM for a first layer, two for a hidden one
+    "harl_mlp_rect_act_tangent": lambda a: 2.0 * (2 if a[0] else 1) * a[2] * a[7] * a[4],
     "harl_mlp_rect_linear_groups": lambda a: 2.0 * a[1] * a[2] * sum(a[4][g] for g in range(a[3])),
     "harl_mlp_rect_bwd_groups": lambda a: 2.0 * a[7] * a[8] * sum(a[2][g] for g in range(a[1])),
     "harl_mlp_rect_tangent_groups": lambda a: 2.0 * 2 * a[2] * a[3] * sum(a[5][g] for g in range(a[4])),  # two GEMMs per group

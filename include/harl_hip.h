@@ -235,6 +235,18 @@ int harl_mlp_rect_act_bwd(const float *dz, const float *xprev, const float *mean
 int harl_mlp_rect_tangent(const float *xin_dot, const float *xin, long M, int KP, int HO, const float *Wp, const float *Wdp,
                           int D, const float *bdp, const float *xprimal, const uint32_t *mask_in, const float *rstd_in,
                           float *xout_dot, void *stream);
+/* ... and of such a layer with an activation other than ReLU (HATRPO on the networks of harl_mlp_rect_act_fwd; opt-in
+ * HARL_TRPO_ACT_256=1 next to HARL_ACT_256=1): x_out_dot = LNjac(act'(a) . (Wdp x_in + bdp [+ Wp x_in_dot])) with a = xprimal /
+ * rstd_in + mean_in, the value harl_mlp_rect_act_bwd rebuilds from the same record with the same arithmetic, and act' taken
+ * from it.  k_panel_rect<MT, 2, ACT>: the stream of harl_mlp_rect_tangent, the slope multiplied into the accumulators in the
+ * epilogue -- the role of two harl_mlp_linear and one harl_act_ln_tangent, without their two pre-activation images.  Arguments
+ * of harl_mlp_rect_tangent with act (1..4, as above) added and mean_in in the place of the mask words; EVERY layer of such a
+ * network: a first layer (x_in_dot = NULL, Wp unused, KP a multiple of 32, 1 <= D <= KP <= 512) may have HO = 256 as well, a
+ * hidden one has KP = D = 64 / 128 / 256.  Other shapes or another act: -2 and an error text.  Nothing is allocated, nothing
+ * synchronises. */
+int harl_mlp_rect_act_tangent(const float *xin_dot, const float *xin, long M, int KP, int HO, const float *Wp, const float *Wdp,
+                              int D, const float *bdp, int act, const float *xprimal, const float *mean_in, const float *rstd_in,
+                              float *xout_dot, void *stream);
 /* A grouped head on a trunk that holds a 256-wide layer (opt-in HARL_CAT_WIDE_256=1): the Categorical(hidden, n) of a
  * Discrete(n) space with 65 <= n <= 512 (harl/models/base/act.py:24-43 with distributions.py:37-55), cut into n_groups <= 4
  * groups of sp_g = 64 / 128 rows as described at harl_cat_head_logp below.  sp, Wp, bp, z, dz: HOST arrays of n_groups entries

@@ -190,6 +190,13 @@ def main():
             (f"h17_rect_relu_bwd_{ho}to{hi}", lambda hi=hi, ho=ho: call("harl_mlp_rect_bwd", ptr(yb), ptr(ya), ptr(mask4_), ptr(rstd2_), B2, ho, hi, ptr(Wr), ptr(yo), s), f),
             (f"h17_rect_tanh_bwd_{ho}to{hi}", lambda hi=hi, ho=ho: call("harl_mlp_rect_act_bwd", ptr(yb), ptr(ya), ptr(mean_o), ptr(rstd2_), B2, ho, hi, 2, ptr(Wr), ptr(yo), s), f),
         ]
+    # ---- HARL_TRPO_ACT_256=1: k_panel_rect<MT, 2, ACT> with the tanh slope in its epilogue; the ReLU tangent of the same shape and
+    # rows is h17_tangent_rect_* above (filter "tangent_rect_2" with --lib on another build: the yardstick of
+    # profiles/r22_trpo_act_256.md)
+    for hi, ho in ((256, 128), (256, 256)):
+        jobs.append((f"h17_tangent_rect_tanh_{hi}to{ho}", lambda hi=hi, ho=ho: call(
+            "harl_mlp_rect_act_tangent", ptr(yb), ptr(ya), B2, hi, ho, ptr(Wr), ptr(Wrd), hi, ptr(br), 2, ptr(yc), ptr(mean_o), ptr(rstd2_),
+            ptr(yo), s), GF(2 * 2.0 * B2 * hi * ho)))
     print(f"B={B}  H={H}  reps={args.reps}  lib={_lib.LIB_PATH}")
     for name, fn, (unit, work) in jobs:
         if args.filters and not any(f in name for f in args.filters):
