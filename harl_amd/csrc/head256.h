@@ -1,0 +1,11 @@
+// head256.h -- launcher of the 33..64-output action head on a 256-wide head input (head256.hip), called by dispatch_actor
+// (heads.hip).  ActorArgs lives in an unnamed namespace (heads_common.h), so the argument block crosses the translation units
+// as a pointer to its bytes: both sides include the same definition.
+#pragma once
+#include "common.h"
+
+namespace harl {
+// `actor_args`: the caller's ActorArgs, filled as for every other actor head kernel (act_dim in [33, 64], dw_part = NULL;
+// Gaussian training: part_ls set).  The caller checks the launch (check_launch).
+void launch_head256(const void *actor_args, bool discrete, bool train, int grid, hipStream_t s);
+}  // namespace harl

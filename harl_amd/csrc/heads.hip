@@ -21,6 +21,7 @@
 using namespace harl;
 
 #include "heads_common.h"
+#include "head256.h"
 
 namespace {
 
@@ -625,6 +626,10 @@ int dispatch_actor(const ActorArgs &A, int H, int discrete, int grid, hipStream_
       set_error("actor head: Gaussian heads of 33..64 dimensions train through harl_actor_head_loss_ls (part_ls, dw_part = NULL)");
       return -2;
     }
+    if (H == 256) {  // x_hat_L streamed through the matrix pipe instead of held in registers (csrc/head256.hip)
+      launch_head256(&A, false, TRAIN, grid, s);
+      return check_launch("harl_actor_head");
+    }
     if (H != 64 && H != 128) {
       set_error("actor head: Gaussian heads of 33..64 dimensions need a hidden width of 64 or 128");
       return -2;
@@ -658,6 +663,10 @@ int dispatch_actor(const ActorArgs &A, int H, int discrete, int grid, hipStream_
   if (dap == 64 && (H == 64 || H == 128)) {  // Categorical only (checked above)
     if (H == 64) launch_actor<64, 64, true, TRAIN>(A, grid, s);
     else launch_actor<128, 64, true, TRAIN>(A, grid, s);
+    return check_launch("harl_actor_head");
+  }
+  if (dap == 64 && H == 256) {  // (csrc/head256.hip)
+    launch_head256(&A, true, TRAIN, grid, s);
     return check_launch("harl_actor_head");
   }
   set_error("actor head: hidden width must be 64 or 128");

@@ -64,7 +64,7 @@ class OnPolicyBase:
         head (Gaussian / Categorical of up to 64 actions), no data parallelism.  Everything else stays eager, exactly as without
         the variable."""
         return (graphs.enabled() and not (self.use_recurrent_policy or self.use_naive_recurrent_policy)
-                and not self.actor.recurrent and not self.actor.grouped and not self.actor.gauss_wide
+                and not self.actor.recurrent and not self.actor.grouped and not self.actor.gauss_wide and not self.actor.head64_256
                 and not self.comm.enabled and self.shard is None)
 
     def _graph_stage(self, name: str, t: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
@@ -345,7 +345,7 @@ class HAPPO(OnPolicyBase):
                                           logp_out=logp_out)
             self._optimizer_step(nblk)
         if not _graph:
-            if (self.actor.cat_wide or self.actor.gauss_wide) and graphs.enabled():  # HARL_GRAPH=1: these heads run eagerly, and say so
+            if (self.actor.cat_wide or self.actor.gauss_wide or self.actor.head64_256) and graphs.enabled():  # HARL_GRAPH=1: these heads run eagerly, and say so
                 self._graph.eager_steps += 1
             return step()
         # HARL_GRAPH=1 (graphs.py): replay this step from a hipGraph.  Eager all the same: the epoch-0 step that also emits the

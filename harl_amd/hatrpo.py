@@ -18,7 +18,7 @@ import torch
 from . import _lib
 from ._lib import call, ptr, stream
 from .buffers import OnPolicyActorBuffer, consume_randperm, rng_sync
-from .configs import (ACT_256_REFUSALS, CAT_WIDE_REFUSALS, GAUSS_WIDE_REFUSALS, MIXED_256_REFUSALS, act_256_applies, gauss_wide_enabled, is_mixed_256,
+from .configs import (ACT_256_REFUSALS, CAT_WIDE_REFUSALS, GAUSS_WIDE_REFUSALS, MIXED_256_REFUSALS, act_256_applies, gauss_wide_enabled, head64_256_applies, head64_256_reason, is_mixed_256,
                       mixed_256_enabled, trpo_act_256_enabled, trpo_cat_wide_256_enabled, trpo_cat_wide_enabled, trpo_mixed_256_enabled)
 from .happo import OnPolicyBase
 from .nets import build_seq, consume_policy_init_rng, seq_compact
@@ -38,6 +38,10 @@ class HATRPO(OnPolicyBase):
             raise NotImplementedError(MIXED_256_REFUSALS["hatrpo"])  # (the tangent of a rectangular pair is opt-in: _fvp)
         if act_256_applies(list(args["hidden_sizes"]), args.get("activation_func", "relu")) and not trpo_act_256_enabled():
             raise NotImplementedError(ACT_256_REFUSALS["hatrpo"])  # (HARL_ACT_256=1 opens these networks to the other algorithms; their tangent, _fvp, is opt-in)
+        if act_space.__class__.__name__ in ("Discrete", "Box") and not (args["use_recurrent_policy"] or args["use_naive_recurrent_policy"]):
+            n = int(act_space.n) if act_space.__class__.__name__ == "Discrete" else int(act_space.shape[0])
+            if head64_256_applies(list(args["hidden_sizes"]), n, act_space.__class__.__name__ == "Box"):
+                raise NotImplementedError(head64_256_reason(args.get("activation_func", "relu"), "hatrpo"))  # (HARL_HEAD64_256=1: no head tangent at 64 outputs on 256)
         super().__init__(args, obs_space, act_space, device)  # (HARL_TRPO_CAT_WIDE=1: n > 512, 256-wide and non-ReLU are refused there)
         if self.actor.cat_wide and self.actor.recurrent and self.actor.gru_wide:
             raise NotImplementedError(CAT_WIDE_REFUSALS["hatrpo_gru_wide"])

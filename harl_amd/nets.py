@@ -24,7 +24,7 @@ from . import _lib
 from . import graphs as _graphs
 from ._lib import DHEAD_LD, PS_STRIDE, SLAB, call, ptr, stream
 from .configs import (ACT_256_REFUSALS, GAUSS_WIDE_REFUSALS, act_256_applies, act_256_reason, bwd_k64, bwd_streams, cat_wide_reason,
-                      gauss_wide_enabled, gauss_wide_reason, gru_dw6, is_mixed_256, mixed_256_enabled, mixed_256_reason,
+                      gauss_wide_enabled, gauss_wide_reason, gru_dw6, head64_256_applies, head64_256_reason, is_mixed_256, mixed_256_enabled, mixed_256_reason,
                       trunk_dw_stream)
 
 SUPPORTED_WIDTHS = (64, 128, 256)
@@ -205,6 +205,7 @@ class _FlatNet(nn.Module):
         self.md = False  # MultiDiscrete heads (StochasticPolicy)
         self.cat_wide = False  # Categorical head of 65..512 actions, cut into groups of 128 rows (StochasticPolicy)
         self.gauss_wide = False  # Gaussian head of 33..64 dimensions, HARL_GAUSS_WIDE=1 (StochasticPolicy)
+        self.head64_256 = False  # plain head of 33..64 outputs on a 256-wide last layer, HARL_HEAD64_256=1 (StochasticPolicy)
         self._md_sp: List[int] = []  # image width of every head GROUP (MultiDiscrete / wide Categorical), empty otherwise
         self._cpu_params: List[Tuple[str, torch.Tensor]] = []
         self._build_trunk_params(args)
@@ -1247,8 +1248,15 @@ class StochasticPolicy(_FlatNet):
         if not self.grouped and not self.gauss_wide and (self.act_dim > 64 or (self.act_dim > 32 and not self.discrete)):
             raise NotImplementedError("action heads wider than 32 (Categorical: 64) are not instantiated")
         self.wide_head = (not self.grouped) and self.act_dim > 32
-        if self.mixed_256 and self.wide_head:  # (the head kernels of a 256-wide last layer stop at 32 outputs)
-            why = mixed_256_reason(self.hidden_sizes, head=self.act_dim)
+        if self.mixed_256 and self.wide_head:  # (the head kernels of a 256-wide last layer stop at 32 outputs without HARL_HEAD64_256=1)
+            why = mixed_256_reason(self.hidden_sizes, head=self.act_dim, gaussian=not self.discrete)
+            if why is not None:
+                raise NotImplementedError(why)
+        # HARL_HEAD64_256=1: a plain head of 33..64 outputs on a 256-wide last layer (k_head256, csrc/head256.hip) -- the launches of
+        # every other plain head with fh = 256, the ATL(64) dhead image and, for a Gaussian one, the part_ls rows (_ensure_ws)
+        self.head64_256 = self.wide_head and not self.recurrent and head64_256_applies(self.hidden_sizes, self.act_dim, not self.discrete)
+        if self.head64_256:
+            why = head64_256_reason(self.activation_func)
             if why is not None:
                 raise NotImplementedError(why)
         self._finalize_params()
@@ -1348,6 +1356,14 @@ class StochasticPolicy(_FlatNet):
     # that tells the three kinds of head apart -- plain (Gaussian, Categorical of up to 64 actions: csrc/heads.hip), MultiDiscrete
     # groups (self.md) and a Categorical of 65..512 actions (self.cat_wide), the two whose logits md_logits launches first.
     # Row arrays are tensors or None; m_valid / m_pad: the padded sequences of a recurrent batch (0, 0 otherwise).
+    def _plain_head_input(self, name: str):
+        """feat() for the plain head's launches.  Without HARL_HEAD64_256=1 a head of 33..64 outputs on a 256-wide last layer
+        ends here as it always did at its first launch: the library's kernel for it is the switch's to open."""
+        f = self.feat()
+        if self.wide_head and f[3] == 256 and not self.head64_256:
+            raise RuntimeError(f"{name} failed (-2): actor head: hidden width must be 64 or 128")
+        return f
+
     def dist_args(self):
         """(log_std, std_x_coef, std_y_coef, discrete, act_dim): the distribution arguments of the plain head's kernels."""
         return ptr(self.log_std()), self.std_x_coef, self.std_y_coef, int(self.discrete), self.act_dim
@@ -1366,7 +1382,7 @@ class StochasticPolicy(_FlatNet):
                  0 if old_logp is None else old_logp.shape[1], ptr(factor), agg, ptr(head_out), m_valid, m_pad, stream(),
                  tag="md_head_logp")
         else:
-            fx, _, _, fh = self.feat()
+            fx, _, _, fh = self._plain_head_input("harl_actor_head_logp")
             Wp, bp = self._packs[-1]
             call("harl_actor_head_logp", ptr(fx), M, fh, ptr(Wp), ptr(bp), *self.dist_args(), ptr(actions), ptr(avail),
                  ptr(logp_out), ptr(old_logp), ptr(factor), agg, ptr(head_out), m_valid, m_pad, stream(), tag="actor_head_logp")
@@ -1395,7 +1411,7 @@ class StochasticPolicy(_FlatNet):
                  ptr(adv_moments), ptr(factor), ptr(active), ptr(md_ent_scale()), clip, ent_coef, agg, mode, m_valid, m_pad,
                  ptr(logp_out), ptr(self.part_scalars), nblk, s, tag="md_head_loss")
             return nblk, False
-        fx, fmask, frstd, fh = self.feat()
+        fx, fmask, frstd, fh = self._plain_head_input("harl_actor_head_loss")
         Wp, bp = self._packs[-1]
         if self.gauss_wide:  # 33..64 dimensions: no fused head gradient, the log_std sums in self.part_ls (ls_reduce)
             call("harl_actor_head_loss_ls", ptr(fx), ptr(fmask), ptr(frstd), M, fh, ptr(Wp), ptr(bp), *self.dist_args(), ptr(idx),

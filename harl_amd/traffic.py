@@ -164,13 +164,17 @@ def _actor_head_loss(a: Sequence) -> float:
     M, H, disc, ad = a[3], a[4], a[10], a[11]
     w = 1 if disc else ad
     return M * (_act(H) + _head_rows(disc, ad, a[14]) + 4.0 + (4.0 if a[18] else 0.0) + (4.0 if a[19] else 0.0)
-                + (4.0 * w if a[26] else 0.0) + 4.0 * H + (4.0 * 32 if (a[28] and not a[30]) else 0.0))  # dhead only when the head dW is not fused
+                + (4.0 * w if a[26] else 0.0) + 4.0 * H
+                # dhead only when the head dW is not fused: [M][32] rows, the ATL(64) image for a head of more than 32 outputs.
+                # H = 256 with 33..64 outputs (k_head256, csrc/head256.hip): x_hat_L is read a second time by the backward's
+                # panels, from L2 -- the wave read the slab a few microseconds earlier -- so the model counts it once, as here.
+                + (4.0 * (64 if ad > 32 else 32) if (a[28] and not a[30]) else 0.0))
 
 
 def _actor_head_loss_ls(a: Sequence) -> float:
-    # harl_actor_head_loss's arguments + part_ls in front of the stream: dhead is the ATL(64) image, not [M][32] rows
-    # (actions and stored log-probs are read twice, the second time from cache)
-    return _actor_head_loss(a) + a[3] * 4.0 * 32
+    # harl_actor_head_loss's arguments + part_ls in front of the stream (dhead is the ATL(64) image: counted there; actions and
+    # stored log-probs are read twice, the second time from cache)
+    return _actor_head_loss(a)
 
 
 def _actor_head_logp(a: Sequence) -> float:

@@ -197,6 +197,33 @@ def main():
         jobs.append((f"h17_tangent_rect_tanh_{hi}to{ho}", lambda hi=hi, ho=ho: call(
             "harl_mlp_rect_act_tangent", ptr(yb), ptr(ya), B2, hi, ho, ptr(Wr), ptr(Wrd), hi, ptr(br), 2, ptr(yc), ptr(mean_o), ptr(rstd2_),
             ptr(yo), s), GF(2 * 2.0 * B2 * hi * ho)))
+    # ---- HARL_HEAD64_256=1: plain heads of 33 and 64 outputs on a 256-wide head input (k_head256, csrc/head256.hip) -- log-prob
+    # pass, loss + backward, and the head's weight gradient from the ATL(64) dhead image -- next to the 32-output head of
+    # csrc/heads.hip on the same rows (the yardstick of profiles/r23_head64_256.md)
+    nb2 = _lib.load().harl_head_blocks(B2)
+    ps2, pls2 = torch.zeros(nb2 * 48, device=dev), torch.zeros(nb2 * 64, device=dev)
+    Wh256, bh64, ls64 = rn(64 * 256) * 0.05, rn(64) * 0.1, torch.ones(64, device=dev)
+    dhead64, lp64 = torch.empty(mp2 * 64, device=dev), torch.empty(B2 * 64, device=dev)
+    adv2, one2 = adv[:B2].contiguous(), factor[:B2].contiguous()
+    for disc, nm in ((1, "cat"), (0, "box")):
+        for D in (32, 33, 64):
+            act_ = torch.randint(0, D, (B2,), device=dev, generator=g).float() if disc else rn(B2, D)
+            olp_ = rn(B2, 1 if disc else D) * 0.1 - 1
+            loss_fn = "harl_actor_head_loss" if (disc or D <= 32) else "harl_actor_head_loss_ls"
+            tail = (s,) if loss_fn == "harl_actor_head_loss" else (ptr(pls2), s)
+            byt = GB(B2 * (1024 + 1024 + 20 + 4 * (64 if D > 32 else 32) + 4 * (2 if disc else 2 * D)))
+            jobs += [
+                (f"h256_{nm}{D}_logp", lambda disc=disc, D=D, act_=act_: call(
+                    "harl_actor_head_logp", ptr(ya), B2, 256, ptr(Wh256), ptr(bh64), ptr(ls64), 1.0, 0.5, disc, D, ptr(act_), None, ptr(lp64),
+                    None, None, 0, None, 0, 0, s), GB(B2 * (1024 + 4 * (2 if disc else 2 * D)))),
+                (f"h256_{nm}{D}_loss", lambda disc=disc, D=D, act_=act_, olp_=olp_, loss_fn=loss_fn, tail=tail: call(
+                    loss_fn, ptr(ya), ptr(mask4_), ptr(rstd2_), B2, 256, ptr(Wh256), ptr(bh64), ptr(ls64), 1.0, 0.5, disc, D, None, ptr(act_),
+                    None, ptr(olp_), ptr(adv2), None, ptr(one2), ptr(one2), 0.2, 0.01, 0, 0, 0, 0, None, ptr(yo), ptr(dhead64), ptr(ps2),
+                    None, 0, *tail), byt),
+            ]
+            if D == 64 and disc:  # (the same launch for both kinds of head and every width above 32)
+                jobs.append(("h256_dw_head_atl64", lambda: call("harl_mlp_dw_partials", ptr(dhead64), 0, 0, 64, ptr(ya), 0, 0, None, None,
+                                                                     None, 256, B2, ptr(part), n_wg, s), GB(B2 * (1024 + 256))))
     print(f"B={B}  H={H}  reps={args.reps}  lib={_lib.LIB_PATH}")
     for name, fn, (unit, work) in jobs:
         if args.filters and not any(f in name for f in args.filters):
