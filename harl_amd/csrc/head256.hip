@@ -262,6 +262,207 @@ __global__ __launch_bounds__(WG_THREADS, 1) void k_head256(ActorArgs A) {
   }
 }
 
+// =============================================================================================
+// HATRPO Fisher-vector product, head part, for a Categorical head of 33..64 actions on a 256-wide head input
+// (k_actor_head_fvp<H, 64, true>'s arithmetic, heads.hip; trpo_util.py:132-158), built like k_head256: neither x_hat_L nor its
+// tangent is ever held whole.
+//
+//   forward   z = W' x_hat, zd = W'_dot x_hat + W' x_hat_dot in ONE sweep over both ATL images, each read from HBM once per slab,
+//             on the MFMA form of head256_fwd with BOTH weight images resident in LDS (wl, wdl: [64][256 + 4] each).  Per k-step
+//             and output tile three products; the A fragment of W' serves both B operands and the B fragment of x_hat both A
+//             fragments: 768 MFMAs per slab.  The images stream a QUARTER of a slab ahead (two K panels of 32 features, eight
+//             float4 per image): with 2 x 128 accumulator registers a half of two images (128 registers current + 128
+//             prefetched) does not fit next to them.
+//   chains    z keeps head256_fwd's four chains per tile -- K panel p of the slab on chain p & 3, in head256_fwd's order, so z
+//             is head256_fwd's z bit for bit.  zd gets TWO per tile, K panel p on chain p & 1, both of its products on the chain
+//             of their panel (the W'_dot x_hat products are issued with z's, the W' x_hat_dot ones four MFMAs later): 192
+//             accumulator registers.  With four chains for zd as well (256: every AGPR) the compiler kept 12 .. 16 bytes of
+//             scratch per lane whatever else was tried (profiles/r24_trpo_head64_256.md); zd enters dzh linearly, without the
+//             cancellation that made z's chain length matter.  The K loop is unrolled whole: rolled over the halves, the
+//             accumulators were spilled at the loop's back edge.
+//   exchange  one v_permlane32_swap per accumulator register, for z (kept before the bias: zlin) and for zd (+ b'_dot).
+//   Hessian   k_actor_head_fvp's Categorical branch in registers; the availability row is folded into two mask words per lane
+//             BEFORE the sweep, entries >= act_dim take part as logits of -1e10 like unavailable ones (exp = 0 exactly: the sums
+//             are those of the d < act_dim loops), and the masked logit is re-formed from zlin where it is used, so that next to
+//             zd and dzh only zlin is live.
+//   backward  store_dhead<64>, s1 / s2, head256_bwd -- unchanged; the next slab's first quarter is requested in front of it.
+// =============================================================================================
+constexpr int CST256 = 5 * LS_W;  // a stage_head256 constant block: bias at 0, row sums at 4 * 64
+
+// Quarter `u` of a slab's K range (features 64 u .. 64 u + 63 = two K panels of 32): the eight float4 of a lane
+__device__ __forceinline__ void load_kquarter(const float *__restrict__ xL, long slab, int u, int lane, f32x4 (&x)[8]) {
+  const f32x4 *xp = reinterpret_cast<const f32x4 *>(xL + slab * (long)(H256 * SLAB)) + (8 * u) * WAVE + lane;
+#pragma unroll
+  for (int q = 0; q < 8; ++q) x[q] = xp[q * WAVE];
+}
+
+// zl[d] = sum_f x_hat[f] W'[d][f] (no bias) and zd[d] = b'_dot[d] + sum_f (x_hat[f] W'_dot[d][f] + x_hat_dot[f] W'[d][f]), in
+// both lanes of a sample.  xn / xdn: the first K quarter of this slab's two images on entry.
+__device__ __forceinline__ void head256_fvp_fwd(const float *__restrict__ xL, const float *__restrict__ xLd, long slab, int lane, const float *wl, const float *wdl, const float *cdt, f32x4 (&xn)[8],
+                                                f32x4 (&xdn)[8], float (&zl)[LS_W], float (&zd)[LS_W]) {
+  const int i = lane & 31, h = lane >> 5;
+  const float *wa = wl + i * WLD + 4 * h, *wda = wdl + i * WLD + 4 * h;  // A[m = i][k = h], as head256_fwd
+  f32x16 acc[8], accd[4];  // [chain][tile]: four chains for z, two for zd
+#pragma unroll
+  for (int t = 0; t < 8; ++t)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      acc[t][r] = 0.f;
+      if (t < 4) accd[t][r] = 0.f;
+    }
+#pragma unroll
+  for (int g = 0; g < 2; ++g) {
+#pragma unroll
+    for (int uu = 0; uu < 2; ++uu) {  // quarter u = 2 g + uu: K panels 2 u, 2 u + 1 -> chains 2 uu, 2 uu + 1
+      f32x4 xv[8], xdv[8];
+#pragma unroll
+      for (int q = 0; q < 8; ++q) {
+        xv[q] = xn[q];
+        xdv[q] = xdn[q];
+      }
+      if (uu == 0 || g == 0) {  // (the next slab's first quarter is requested behind the Hessian: k_head256_fvp)
+        load_kquarter(xL, slab, 2 * g + uu + 1, lane, xn);
+        load_kquarter(xLd, slab, 2 * g + uu + 1, lane, xdn);
+      }
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        f32x4 a[4], ad[4];  // [panel jj][tile]
+#pragma unroll
+        for (int jj = 0; jj < 2; ++jj)
+#pragma unroll
+          for (int t = 0; t < 2; ++t) {
+            const int o = 32 * t * WLD + 128 * g + 64 * uu + 32 * jj + 8 * q;
+            a[2 * jj + t] = *reinterpret_cast<const f32x4 *>(wa + o);
+            ad[2 * jj + t] = *reinterpret_cast<const f32x4 *>(wda + o);
+          }
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+#pragma unroll
+          for (int jj = 0; jj < 2; ++jj)
+#pragma unroll
+            for (int t = 0; t < 2; ++t) {
+              const int ch = 2 * (2 * uu + jj) + t;
+              acc[ch] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[2 * jj + t][c], xv[4 * jj + q][c], acc[ch], 0, 0, 0);
+              accd[2 * jj + t] = __builtin_amdgcn_mfma_f32_32x32x2f32(ad[2 * jj + t][c], xv[4 * jj + q][c], accd[2 * jj + t], 0, 0, 0);
+            }
+#pragma unroll
+          for (int jj = 0; jj < 2; ++jj)
+#pragma unroll
+            for (int t = 0; t < 2; ++t) {
+              accd[2 * jj + t] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[2 * jj + t][c], xdv[4 * jj + q][c], accd[2 * jj + t], 0, 0, 0);
+            }
+        }
+        __builtin_amdgcn_sched_barrier(0);  // (the weight reads of later steps stay where they are: hoisted, they spill)
+      }
+    }
+  }
+  // (register r of tile t: output d0 = 32 t + (r & 3) + 8 (r >> 2) in lane half 0, d0 + 4 in half 1 -- see head256_fwd)
+  asm volatile("" : "+v"(cdt));  // (one base register and immediate offsets: as constants the 64 LDS addresses sit in SGPRs, which spill)
+#pragma unroll
+  for (int t = 0; t < 2; ++t)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int d0 = 32 * t + (r & 3) + 8 * (r >> 2);
+      const unsigned u = __float_as_uint((acc[t][r] + acc[2 + t][r]) + (acc[4 + t][r] + acc[6 + t][r]));
+      const unsigned ud = __float_as_uint(accd[t][r] + accd[2 + t][r]);
+      const auto p = __builtin_amdgcn_permlane32_swap(u, u, false, false);
+      const auto pd = __builtin_amdgcn_permlane32_swap(ud, ud, false, false);
+      zl[d0] = __uint_as_float(p[0]);
+      zl[d0 + 4] = __uint_as_float(p[1]);
+      zd[d0] = __uint_as_float(pd[0]) + cdt[d0];
+      zd[d0 + 4] = __uint_as_float(pd[1]) + cdt[d0 + 4];
+    }
+  __builtin_amdgcn_sched_barrier(0);  // (nothing of the Hessian moves up between the MFMAs, as in head256_fwd)
+}
+
+__global__ __launch_bounds__(WG_THREADS, 1) void k_head256_fvp(FvpArgs A) {
+  constexpr int DAP = LS_W;
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  float *wl = lds;               // [64][WLD]  W'
+  float *wdl = wl + DAP * WLD;   // [64][WLD]  W'_dot
+  float *cst = wdl + DAP * WLD;  // bias, row sums of W'
+  float *cdt = cst + CST256;     // bias_dot (+ the row sums of W'_dot, unused)
+  stage_head256(wl, cst, A.Whp, A.bhp, A.act_dim);
+  stage_head256(wdl, cdt, A.Whdp, A.bhdp, A.act_dim);
+  __syncthreads();
+
+  const int lane = threadIdx.x & 63, wave = wave_id();
+  const int i = lane & 31;
+  const int D = A.act_dim;
+  const long slab_first = (long)blockIdx.x * WAVES_PER_WG + wave, slab_step = (long)gridDim.x * WAVES_PER_WG;
+  f32x4 xn[8], xdn[8];
+  if (slab_first < A.n_slabs) {
+    load_kquarter(A.xL, slab_first, 0, lane, xn);
+    load_kquarter(A.xLdot, slab_first, 0, lane, xdn);
+  }
+  for (long slab = slab_first; slab < A.n_slabs; slab += slab_step) {
+    const long next = slab + slab_step < A.n_slabs ? slab + slab_step : slab;
+    int ls = 0;
+    asm volatile("" : "+v"(ls));
+    ls = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, ls));  // (a slab's addresses are formed in the slab: carried from the kernel's top, they spill)
+    // bit d of un[d >> 5]: entry d exists and is available (the row is read in front of the product; clamped index: no load
+    // under a per-entry branch)
+    uint32_t un[2] = {0u, 0u};
+    {
+      const long j = slab * SLAB + (ls & 31);
+      const long jc = j < A.M ? j : A.M - 1;  // (a padding sequence's own row instead of row M - 1: its dzh is 0 either way)
+      const float *av = A.avail ? A.avail + jc * D : A.Whp;  // (absent: a mapped dummy row, not consulted)
+#pragma unroll
+      for (int c = 0; c < DAP / 16; ++c) {
+        int Dc = D;
+        asm volatile("" : "+s"(Dc));  // opaque per chunk: hoisted out of the slab loop, the 64 width tests live in SGPRs that spill
+#pragma unroll
+        for (int k = 0; k < 16; ++k) {
+          const int d = 16 * c + k;
+          const float v = av[d < Dc ? d : 0];
+          if (d < Dc && !(A.avail && v == 0.f)) un[d >> 5] |= 1u << (d & 31);
+        }
+        __builtin_amdgcn_sched_barrier(0);  // (sixteen loads in flight at a time, and none between the MFMAs)
+      }
+    }
+    float zl[DAP], zd[DAP], dzh[DAP];
+    head256_fvp_fwd(A.xL, A.xLdot, slab, ls, wl, wdl, cdt, xn, xdn, zl, zd);
+
+    // Entries >= D ride along at -1e10 like unavailable ones: the maximum is an available logit, so their exp is exactly 0 and
+    // every sum below is the sum of k_actor_head_fvp's d < D loop.  Four sweeps of four chunks: the mask word is re-read as an
+    // opaque value per chunk and nothing crosses a chunk's end -- left free, hipcc keeps the 64 lane masks of the first sweep
+    // in SGPRs for the other three and interleaves all 128 exponentials, and both spill.
+#define HEAD256_FVP_CHUNK(BODY)                                                   \
+  _Pragma("unroll") for (int c = 0; c < DAP / 16; ++c) {                          \
+    uint32_t w = un[c >> 1] >> (16 * (c & 1));                                    \
+    const float *cs = cst;                                                        \
+    asm volatile("" : "+v"(w), "+v"(cs)); /* (cs: immediate offsets from ONE base) */  \
+    _Pragma("unroll") for (int k = 0; k < 16; ++k) {                              \
+      const int d = 16 * c + k;                                                   \
+      const bool open = (w >> k) & 1u;                                            \
+      const float zm = open ? zl[d] + cs[d] : -1e10f;  /* the masked logit */     \
+      BODY                                                                        \
+    }                                                                             \
+    __builtin_amdgcn_sched_barrier(0);                                            \
+  }
+    float mx = -3.0e38f;
+    HEAD256_FVP_CHUNK(mx = fmaxf(mx, zm);)
+    float se = 0.f;
+    HEAD256_FVP_CHUNK(se += expf(zm - mx);)
+    const float lse = mx + logf(se);
+    float S = 0.f, sum_zd = 0.f;
+    HEAD256_FVP_CHUNK(const float pr = expf(zm - lse); dzh[d] = pr; if (open) { S += pr * zd[d]; sum_zd += zd[d]; })
+    const float sum_dq = sum_zd - (float)D * S;  // sum over ALL D entries of q_dot_d = [unmasked] zd_d - S
+    float s1 = 0.f, s2 = 0.f;
+    int lb = ls;
+    asm volatile("" : "+v"(lb));  // (the row's validity and the backward's addresses are formed here, not carried across the sweep)
+    const long j = slab * SLAB + (lb & 31);
+    const bool valid = j < A.M && (A.m_pad == 0 || (j % A.m_pad) < A.m_valid);
+    HEAD256_FVP_CHUNK((void)zm; dzh[d] = open && valid ? (zd[d] - S) - dzh[d] * sum_dq : 0.f;  // log-softmax backward of dq = q_dot
+                      s1 += dzh[d] * cs[4 * DAP + d]; s2 += dzh[d] * zl[d];)
+#undef HEAD256_FVP_CHUNK
+    store_dhead<DAP>(A.dhead, slab, lb, dzh);
+    load_kquarter(A.xL, next, 0, lb, xn);  // (in flight while the backward's MFMAs run)
+    load_kquarter(A.xLdot, next, 0, lb, xdn);
+    head256_bwd(A.xL, A.relu_mask, A.rstd[slab * SLAB + (lb & 31)], slab, lb, wl, dzh, s1, s2, A.dzL);
+  }
+}
+
 template <bool DISCRETE, bool TRAIN>
 void launch(const ActorArgs &A, int grid, hipStream_t s) {
   size_t fl = (size_t)LS_W * WLD + 7 * LS_W + 4 * PS_STRIDE;  // 65 KiB of weights + constants + the scalar reduction
@@ -282,4 +483,11 @@ void harl::launch_head256(const void *actor_args, bool discrete, bool train, int
     if (train) launch<false, true>(A, grid, s);
     else launch<false, false>(A, grid, s);
   }
+}
+
+void harl::launch_head256_fvp(const void *fvp_args, int grid, hipStream_t s) {
+  const FvpArgs &A = *static_cast<const FvpArgs *>(fvp_args);
+  const size_t shm = ((size_t)2 * LS_W * WLD + 2 * CST256) * sizeof(float);  // two weight images + constants: 132.5 KiB
+  allow_big_lds(k_head256_fvp, shm);
+  hipLaunchKernelGGL(k_head256_fvp, dim3(grid), dim3(WG_THREADS), shm, s, A);
 }

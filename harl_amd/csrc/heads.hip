@@ -413,20 +413,7 @@ __global__ __launch_bounds__(WG_THREADS, FUSE ? 2 : 1) void k_critic_head(Critic
 // followed by the ordinary backward pass.  This kernel: tangent of the head, M, backward through the head and the
 // last LayerNorm/ReLU -> dz_L (ATL) + dhead (for the head dW); the caller divides by the batch size (kl.mean()).
 // =============================================================================================
-struct FvpArgs {
-  const float *xL, *xLdot;
-  const uint32_t *relu_mask;
-  const float *rstd;
-  long M;
-  const float *Whp, *bhp, *Whdp, *bhdp, *log_std;
-  float std_x_coef, std_y_coef;
-  int act_dim;
-  const float *avail;
-  float *dzL, *dhead;
-  long n_slabs;
-  long m_valid, m_pad;  // recurrent batches: rows j with (j % m_pad) >= m_valid are padding sequences
-};
-
+// (FvpArgs: heads_common.h)
 template <int H, int DAP, bool DISCRETE>
 __global__ __launch_bounds__(WG_THREADS) void k_actor_head_fvp(FvpArgs A) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -825,6 +812,10 @@ extern "C" int harl_actor_head_fvp(const float *xL, const float *xLdot, const ui
   if (dap == 64 && (H == 64 || H == 128)) {
     if (H == 64) launch_fvp<64, 64, true>(A, grid, s);
     else launch_fvp<128, 64, true>(A, grid, s);
+    return check_launch("harl_actor_head_fvp");
+  }
+  if (dap == 64 && H == 256) {  // (k_head256_fvp, csrc/head256.hip; Categorical only: checked above)
+    launch_head256_fvp(&A, grid, s);
     return check_launch("harl_actor_head_fvp");
   }
 #define CASE(Hv, DAPv)                                          \

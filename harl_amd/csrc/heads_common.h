@@ -37,6 +37,21 @@ struct ActorArgs {
   float *part_ls;   // Gaussian heads of 33..64 dimensions: per-workgroup log_std sums [gridDim.x][LS_W] (k_gauss_head_wide)
 };
 
+// Head part of HATRPO's Fisher-vector product (k_actor_head_fvp, heads.hip; k_head256_fvp, head256.hip)
+struct FvpArgs {
+  const float *xL, *xLdot;
+  const uint32_t *relu_mask;
+  const float *rstd;
+  long M;
+  const float *Whp, *bhp, *Whdp, *bhdp, *log_std;
+  float std_x_coef, std_y_coef;
+  int act_dim;
+  const float *avail;
+  float *dzL, *dhead;
+  long n_slabs;
+  long m_valid, m_pad;  // recurrent batches: rows j with (j % m_pad) >= m_valid are padding sequences
+};
+
 template <int H, int DAP>
 __device__ __forceinline__ void stage_head(float *whl, float *cst, const float *__restrict__ Whp,
                                            const float *__restrict__ bhp, int act_dim) {

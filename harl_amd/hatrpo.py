@@ -40,8 +40,9 @@ class HATRPO(OnPolicyBase):
             raise NotImplementedError(ACT_256_REFUSALS["hatrpo"])  # (HARL_ACT_256=1 opens these networks to the other algorithms; their tangent, _fvp, is opt-in)
         if act_space.__class__.__name__ in ("Discrete", "Box") and not (args["use_recurrent_policy"] or args["use_naive_recurrent_policy"]):
             n = int(act_space.n) if act_space.__class__.__name__ == "Discrete" else int(act_space.shape[0])
-            if head64_256_applies(list(args["hidden_sizes"]), n, act_space.__class__.__name__ == "Box"):
-                raise NotImplementedError(head64_256_reason(args.get("activation_func", "relu"), "hatrpo"))  # (HARL_HEAD64_256=1: no head tangent at 64 outputs on 256)
+            why = head64_256_reason(args.get("activation_func", "relu"), "hatrpo")  # (the head's tangent at 64 outputs on 256 is opt-in: HARL_TRPO_HEAD64_256=1)
+            if why and head64_256_applies(list(args["hidden_sizes"]), n, act_space.__class__.__name__ == "Box"):
+                raise NotImplementedError(why)
         super().__init__(args, obs_space, act_space, device)  # (HARL_TRPO_CAT_WIDE=1: n > 512, 256-wide and non-ReLU are refused there)
         if self.actor.cat_wide and self.actor.recurrent and self.actor.gru_wide:
             raise NotImplementedError(CAT_WIDE_REFUSALS["hatrpo_gru_wide"])

@@ -567,7 +567,9 @@ int harl_mlp_tangent_hidden2(const float *xin_dot, const float *xin, long M, int
                              const uint32_t *mask_in, const float *rstd_in, float *xout_dot, void *stream);
 /* head tangent, M (Gaussian 1/sigma^2 on the mean; identity on the normalised logits incl. masked entries), head +
  * LayerNorm/ReLU backward -> dzL ATL(H), dhead[M_pad,32]; NOT yet divided by the batch size.  m_valid / m_pad as in
- * harl_actor_head_loss (padding sequences of a recurrent batch get zero gradients; 0, 0 = no padding) */
+ * harl_actor_head_loss (padding sequences of a recurrent batch get zero gradients; 0, 0 = no padding).  Categorical heads of
+ * 33..64 actions write dhead as an ATL(64) image; at H = 256 they run k_head256_fvp (csrc/head256.hip), H = 64 / 128
+ * k_actor_head_fvp. */
 int harl_actor_head_fvp(const float *xL, const float *xLdot, const uint32_t *relu_mask, const float *rstd, long M, int H,
                         const float *Whp, const float *bhp, const float *Whdp, const float *bhdp, const float *log_std,
                         float std_x_coef, float std_y_coef, int discrete, int act_dim, const float *avail, long m_valid,

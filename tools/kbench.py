@@ -224,6 +224,14 @@ def main():
             if D == 64 and disc:  # (the same launch for both kinds of head and every width above 32)
                 jobs.append(("h256_dw_head_atl64", lambda: call("harl_mlp_dw_partials", ptr(dhead64), 0, 0, 64, ptr(ya), 0, 0, None, None,
                                                                      None, 256, B2, ptr(part), n_wg, s), GB(B2 * (1024 + 256))))
+    # ---- HARL_TRPO_HEAD64_256=1: the head part of HATRPO's Fisher-vector product on the same rows -- 33 and 64 actions on
+    # k_head256_fvp (csrc/head256.hip), 32 on k_actor_head_fvp<256, 32, true> (csrc/heads.hip), the nearest existing kernel; the
+    # training pass of k_head256 is h256_cat*_loss above (profiles/r24_trpo_head64_256.md)
+    Whd256, bhd64 = rn(64 * 256) * 0.05, rn(64) * 0.1
+    for D in (32, 33, 64):
+        jobs.append((f"h256_cat{D}_fvp", lambda D=D: call(
+            "harl_actor_head_fvp", ptr(ya), ptr(yb), ptr(mask4_), ptr(rstd2_), B2, 256, ptr(Wh256), ptr(bh64), ptr(Whd256), ptr(bhd64),
+            None, 1.0, 0.5, 1, D, None, 0, 0, ptr(yo), ptr(dhead64), s), GB(B2 * (3 * 1024 + 20 + 4 * (64 if D > 32 else 32)))))
     print(f"B={B}  H={H}  reps={args.reps}  lib={_lib.LIB_PATH}")
     for name, fn, (unit, work) in jobs:
         if args.filters and not any(f in name for f in args.filters):
